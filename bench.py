@@ -16,6 +16,11 @@ rank's h multiexp covers the coefficients it ends with.  Each rank returns its 8
 partial sums, RCCL all-gathers them and rank 0 adds them and assembles the
 proof.  Total work is fixed, so scaling is "strong".
 
+A plain run sets up, warms up, times `--steps` proofs, writes the last proof
+with `--dump-outputs DIR` and prints the line.  `--full` adds the secondary
+legs after the headline (CPU baseline, C5 throughput mode, drop-in / seam /
+EvaluationDomain paths), each under its own switch.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -46,6 +51,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--log-constraints", type=int, default=22)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the 192-byte proof, one "
+                         "float32 per byte) to DIR/proof.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary legs: the CPU baseline, the C5 throughput mode "
+                         "and the drop-in / seam / EvaluationDomain paths (each has its own switch below; without "
+                         "--full none of them runs)")
     ap.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU port on a bounded sample (rank 0)")
     ap.add_argument("--cpu-log-constraints", type=int, default=16)
     ap.add_argument("--cpu-1t-log-constraints", type=int, default=12, help="1-thread CPU sample (0: skip)")
@@ -66,7 +78,21 @@ def parse():
                          "host buffers")
     ap.add_argument("--dropin", type=int, default=1,
                     help="also time bh_prove from host buffers (the drop-in path; 1-GPU runs)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run is the headline only: set up, warm up, time the steps, print the line
+        args.cpu_baseline = args.c5 = args.dropin = 0
+    return args
+
+
+def dump_outputs(path, proof):
+    """--dump-outputs: the timed path's result as a caller receives it, the proof's 192 bytes
+    (A, B, C compressed), one float32 per byte so that two builds compare value for value."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "proof.npy"), np.frombuffer(bytes(proof), dtype=np.uint8).astype(np.float32))
 
 
 def cpu_model():
@@ -409,6 +435,8 @@ def main():
             unions.append(list(ctx.last_stats()[21:23]))
     barrier()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ref)
     # window tables the timed proofs read (rank 0 of N, or every rank's own slices for N > 1)
     st = ctx.last_stats()
     tables = {"used": int(st[10]), "large_multiexps": int(st[11]), "GB": round(st[12] / 1e9, 2),
@@ -606,6 +634,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(ms, 3),
         "higher_is_better": True,
         "scaling": "strong",

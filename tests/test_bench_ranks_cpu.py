@@ -24,7 +24,7 @@ RUNNER = (
 @pytest.mark.parametrize("world", [2, 4])
 def test_bench_multirank_line(tmp_path, world):
     code = RUNNER.format(fakes=os.path.join(ROOT, "tests", "fakes"), bench=os.path.join(ROOT, "bench.py"))
-    args = ["--gpus", str(world), "--log-constraints", "6", "--steps", "3", "--warmup", "1",
+    args = ["--gpus", str(world), "--log-constraints", "6", "--steps", "3", "--warmup", "1", "--full",
             "--cpu-baseline", "0", "--dropin", "0", "--c5", "8", "--c5-log-constraints", "4"]
     comm = tmp_path / "comm"
     comm.mkdir()
@@ -74,6 +74,31 @@ def test_bench_single_gpu_prepares_full_tables(tmp_path):
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["srs_window_tables"]["prepare"] == "full"
     assert abs(d["srs_window_tables"]["GB"] - 31.4) < 0.01
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_the_proof(tmp_path):
+    """Without --full no secondary leg runs, whatever their switches say; --dump-outputs writes the
+    last timed proof (192 bytes, one float32 each), the same from run to run."""
+    import numpy as np
+    code = RUNNER.format(fakes=os.path.join(ROOT, "tests", "fakes"), bench=os.path.join(ROOT, "bench.py"))
+    env = dict(os.environ, FAKE_COMM_DIR=str(tmp_path), FAKE_DEVICES="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    dumps = []
+    for name in ("a", "b"):
+        p = subprocess.run([sys.executable, "-c", code, "--gpus", "1", "--log-constraints", "6", "--steps", "3",
+                            "--warmup", "1", "--c5", "8", "--dump-outputs", str(tmp_path / name)], env=env, cwd=ROOT,
+                           capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0, p.stderr
+        d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["full"] is False
+        assert d["c5"] is None and d["dropin"] is None and d["cpu_baseline"] is None
+        assert os.listdir(tmp_path / name) == ["proof.npy"]
+        proof = np.load(tmp_path / name / "proof.npy")
+        assert proof.dtype == np.float32 and proof.shape == (192,)
+        assert bytes(proof.astype(np.uint8)).hex()[:32] == d["proof_sha_prefix"]
+        dumps.append(proof)
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 def test_bench_rank_fails_on_missing_devices(tmp_path):

@@ -2,6 +2,7 @@
 # GPU box: same-box A/B of library builds on the 2^22 bench (alternating runs).
 #   AB_VARIANTS: space-separated name:path pairs (path empty = the in-tree build), default
 #   "base:ab/libbellman_hip_base.so new:".  AB_ENV_<name>: extra environment for a variant.
+#   AB_ARGS: further bench.py arguments ("--full --dropin 1" adds the drop-in leg to the summary).
 # Output: gpurun_out/ab/<name>_<i>.log and one summary line per run in gpurun_out/ab/summary.txt
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/ab

@@ -4,7 +4,7 @@
 # script (no further GPU step); a test failure (pytest exit 1) does not stop later steps.
 #   kfd      KFD topology properties (queue counts) -- no GPU work
 #   pytest   the -m gpu suite ($PYTEST_ARGS appended)
-#   bench    python bench.py $BENCH_ARGS
+#   bench    python bench.py --full $BENCH_ARGS
 #   port22   oracle port at 2^22 -> port_proofs.json fixture (also copied to tests/golden/) + baseline
 #   port24   the same at 2^24, added to tests/golden/port_proofs.json
 #   rehearse N-rank rehearsal at 2^22 ($REH_ARGS)
@@ -21,7 +21,7 @@ for st in ${STEPS:-pytest bench}; do
   case $st in
     kfd) (grep -H . /sys/class/kfd/kfd/topology/nodes/*/properties > "$O/kfd_props.txt" 2>&1; true) ;;
     pytest) timeout -k 10 1100 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread $PYTEST_ARGS > "$O/pytest.log" 2>&1; ok $? ;;
-    bench) timeout -k 10 600 python -u bench.py $BENCH_ARGS > "$O/bench.log" 2>&1; ok $? ;;
+    bench) timeout -k 10 600 python -u bench.py --full $BENCH_ARGS > "$O/bench.log" 2>&1; ok $? ;;
     port22) timeout -k 10 1100 python -u tools/cpu_baseline_full.py --fixture "$O/port_proofs.json" > "$O/port22.log" 2>&1; ok $?
             cp "$O/port_proofs.json" tests/golden/port_proofs.json ;;
     port24) timeout -k 10 1100 python -u tools/cpu_baseline_full.py --log-constraints 24 --fixture tests/golden/port_proofs.json > "$O/port24.log" 2>&1; ok $?
