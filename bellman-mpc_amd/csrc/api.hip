@@ -535,10 +535,15 @@ bh_status ctx_domain(bh_ctx* ctx, int L, Domain** out) {
     }
     BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
   }
-  uint32_t cst[3 * 9];
+  uint32_t cst[5 * 9];
   fr_to_dev_limbs(d->minv, cst);
   fr_to_dev_limbs(d->zinv, cst + 9);
   fr_to_dev_limbs(Fr::one(), cst + 18);
+  // c's ifft in the H block: m^-1 / Z(g), and the same times 32 for bls12_381-Montgomery input
+  // read in place (as coset_hi32)
+  const Fr minv_zinv = mul(d->minv, d->zinv);
+  fr_to_dev_limbs(minv_zinv, cst + 27);
+  fr_to_dev_limbs(mul(minv_zinv, fr_small(32)), cst + 36);
   BH_TRY_HIP(d->consts.alloc(sizeof cst));
   BH_TRY_HIP(hipMemcpy(d->consts.p, cst, sizeof cst, hipMemcpyHostToDevice));
   *out = d.get();
@@ -604,7 +609,7 @@ static bh_status run_fft(bh_ctx* ctx, Domain* D, FftKind kind, uint32_t* d_a, ui
   const uint32_t* post_lo = nullptr;
   const uint32_t* post_hi = nullptr;
   int post_bits = D->lo_bits;
-  if (kind == IFFT) { post_hi = D->consts.as<uint32_t>(); post_bits = -1; }
+  if (kind == IFFT) { post_hi = D->consts.as<uint32_t>(); post_bits = POW_CONST; }
   if (kind == ICOSET_FFT) { post_lo = D->icoset_lo.as<uint32_t>(); post_hi = D->icoset_hi.as<uint32_t>(); }
   launch_ntt(d_tmp, L, false, tw, post_lo, post_hi, post_bits, ctx->stream);
   BH_TRY_HIP(hipMemcpyAsync(d_a, d_tmp, ((size_t)32) << L, hipMemcpyDeviceToDevice, ctx->stream));
@@ -649,17 +654,28 @@ bh_status run_h_vector(bh_ctx* ctx, Domain* D, uint32_t* d_abc, hipStream_t st, 
                        bool raw_src) {
   const int L = D->L;
   const size_t m = (size_t)1 << L;
-  // prover.rs:214-219: ifft (DIF, omega^-1) with m^-1 * g^i fused = ifft + distribute_powers(g);
-  // then fft (DIT, bit-reversed -> natural) = coset_fft; c's storing pass computes
-  // (a*b - c) / Z(g) into a (prover.rs:221-225: mul_assign, sub_assign, divide_by_z_on_coset)
+  // a, b (prover.rs:214-219): ifft (DIF, omega^-1) with m^-1 * g^i fused = ifft +
+  // distribute_powers(g); then fft (DIT, bit-reversed -> natural) = coset_fft; b's storing pass
+  // computes a*b / Z(g) into a (prover.rs:221-225: mul_assign, divide_by_z_on_coset).
+  // c: its coset_fft, sub_assign and icoset_fft (prover.rs:219-226) collapse to the ifft alone.
+  // c has degree < m, so icoset_fft(coset_fft(c)) = c, and icoset_fft is linear: with K = 1/Z(g)
+  //   h = icoset_fft((A o B - C) K) = icoset_fft(A o B K) - ifft(c) K,
+  // exactly in Fr for every a, b, c.  c' = ifft(c) * K stays in c's third of d_abc, bit-reversed
+  // like the final transform's output, which subtracts it (run_h_final).
   uint32_t* x = d_abc + (size_t)v * m * 8;
-  launch_ntt(x, L, true, D->lv_inv.as<uint32_t>(), nullptr, (raw_src ? D->coset32_full : D->coset_full).as<uint32_t>(),
-             POW_FULL_TABLE, st, src_abc ? src_abc + (size_t)v * m * 8 : nullptr);
-  NttEpilogue e;
+  const uint32_t* src = src_abc ? src_abc + (size_t)v * m * 8 : nullptr;
   if (v == 2) {
-    e.kind = NttEpilogue::AB_MINUS_C;
+    launch_ntt(x, L, true, D->lv_inv.as<uint32_t>(), nullptr, D->consts.as<uint32_t>() + (raw_src ? 36 : 27),
+               POW_CONST, st, src);
+    BH_TRY_HIP(hipGetLastError());
+    return BH_OK;
+  }
+  launch_ntt(x, L, true, D->lv_inv.as<uint32_t>(), nullptr, (raw_src ? D->coset32_full : D->coset_full).as<uint32_t>(),
+             POW_FULL_TABLE, st, src);
+  NttEpilogue e;
+  if (v == 1) {
+    e.kind = NttEpilogue::PRODUCT;
     e.pa = d_abc;
-    e.pb = d_abc + m * 8;
     e.k = D->consts.as<uint32_t>() + 9;
   }
   launch_ntt(x, L, false, D->lv_fwd.as<uint32_t>(), nullptr, nullptr, 0, st, nullptr, e);
@@ -670,8 +686,10 @@ bh_status run_h_vector(bh_ctx* ctx, Domain* D, uint32_t* d_abc, hipStream_t st, 
 bh_status run_h_final(bh_ctx* ctx, Domain* D, uint32_t* d_abc, hipStream_t st, uint32_t* hout) {
   const int L = D->L;
   const size_t m = (size_t)1 << L;
-  // prover.rs:226: icoset_fft = ifft + distribute_powers(g^-1), fused as above (output bit-reversed)
+  // prover.rs:226: icoset_fft = ifft + distribute_powers(g^-1), fused as above (output bit-reversed),
+  // minus c' (run_h_vector, v = 2) at the same position
   NttEpilogue e;
+  e.sub = d_abc + 2 * m * 8;
   if (hout) {
     e.kind = NttEpilogue::SCALARS;
     e.out = hout;

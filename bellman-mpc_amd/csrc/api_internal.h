@@ -71,7 +71,7 @@ struct Domain {
   // the H block's post-scale factors as full m-entry tables (coset, coset x 32, icoset: 36 B per
   // entry, 453 MB at 2^22): one product per element in the storing pass instead of two
   DevBuf coset_full, coset32_full, icoset_full;
-  DevBuf consts;                          // [0] m^-1, [1] 1/Z(g), [2] one
+  DevBuf consts;                          // [0] m^-1, [1] 1/Z(g), [2] one, [3] m^-1 / Z(g), [4] 32 m^-1 / Z(g)
   int lo_bits = 0;
   Fr minv, zinv;
 };
@@ -389,7 +389,8 @@ bh_status download_fr(bh_ctx* ctx, uint32_t* src, size_t n, uint64_t* host);
 bh_status run_h_pipeline(bh_ctx* ctx, Domain* D, uint32_t* d_abc, hipStream_t st, const uint32_t* src_abc = nullptr,
                          uint32_t* hout = nullptr);
 // the same in stages, so that each vector's transforms can be enqueued as its upload lands:
-// run_h_vector(v) for v = 0, 1, 2 in order (v = 2 folds (a*b - c)/Z into a), then run_h_final
+// run_h_vector(v) for v = 0, 1, 2 in order (v = 1 folds a*b/Z into a, v = 2 is c's ifft alone,
+// scaled by 1/Z), then run_h_final (stream-ordered behind all three: it subtracts c's ifft)
 // raw_src: src_abc holds bls12_381 Montgomery words (read in place, the factor 2^5 between the
 // two Montgomery radices folded into the ifft's storing-pass scale); its padding must be zero
 bh_status run_h_vector(bh_ctx* ctx, Domain* D, uint32_t* d_abc, hipStream_t st, const uint32_t* src_abc, int v,

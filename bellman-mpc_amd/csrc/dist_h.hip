@@ -2,6 +2,11 @@
 // ranks, the H block of create_proof (reference src/groth16/prover.rs:210-231):
 //   a, b, c: ifft, coset_fft (domain.rs:81-99, 101-125); a*b - c; divide_by_z_on_coset
 //   (domain.rs:139-151); icoset_fft.
+// As on one device (run_h_vector, api.hip), c takes only its ifft: with K = 1/Z(g),
+//   h = icoset_fft(A o B K) - ifft(c) K,
+// so c leaves the pipeline after the first exchange: k_dist_mid keeps c' = ifft(c) K for this
+// rank's q chunk (the index set k_dist_final writes h for), the second exchange carries a and b
+// only (2*M*32 bytes per rank instead of 3*M*32), and k_dist_final subtracts c'.
 //
 // Index algebra (m = N*M, omega of order m, n = N*j + r, k = M*t + q):
 //   inverse  X[M t + q] = sum_r w_N^(-r t) * w^(-r q) * Y_r[q],  Y_r = iNTT_M(x[N j + r])
@@ -20,6 +25,8 @@ struct DistArgs {
   const uint32_t* sc_lo;   // power table over the global index k (g^k m^-1 or g^-k m^-1): split, or
   const uint32_t* sc_hi;   // full in sc_hi (sc_bits = POW_FULL_TABLE, pow_factor)
   int sc_bits;
+  const uint32_t* ck;      // m^-1 / Z(g) (9 limbs): c's ifft scale (k_dist_mid)
+  uint32_t* cprime;        // c' = ifft(c) / Z(g) at [t*C + u] for k = t*M + q (hbuf's layout), M elements
   uint32_t wN[16][9], wNinv[16][9];  // w_N^k, w_N^-k (device Montgomery limbs)
 };
 
@@ -86,6 +93,7 @@ __global__ void __launch_bounds__(256) k_gather_class(const uint32_t* full, uint
 // after exchange 1: received Y_r[q] (r = source rank) for q in this rank's chunk.
 // inverse N-DFT over r (with w^(-r q)), scale g^k m^-1 (ifft + distribute_powers), forward
 // N-DFT over t (with w^(q r')) -> out[vec*M + r'*C + u], row r' bound for rank r'.
+// vec 2 (c) ends after the inverse DFT: scaled by the constant m^-1 / Z(g) into cprime, nothing sent.
 template <int N>
 __global__ void __launch_bounds__(256) k_dist_mid(const uint32_t* recv, uint32_t* out, DistArgs a, uint32_t nvec) {
   const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -98,6 +106,12 @@ __global__ void __launch_bounds__(256) k_dist_mid(const uint32_t* recv, uint32_t
   for (int r = 0; r < N; r++) x[r] = ld_packed(recv, base + (size_t)r * a.C);
   geometric<N>(x, ld_limbs(a.tw_inv, q));
   small_dft<N>(x, a.wNinv);
+  if (vec == 2) {
+    const DFr ck = ld_limbs(a.ck, 0);
+#pragma unroll
+    for (int t = 0; t < N; t++) st_packed(a.cprime, (size_t)t * a.C + u, fe_mul<FrCfg>(x[t], ck));
+    return;
+  }
 #pragma unroll
   for (int t = 0; t < N; t++) x[t] = fe_mul<FrCfg>(x[t], pow_factor(a.sc_lo, a.sc_hi, a.sc_bits, t * a.M + q));
   small_dft<N>(x, a.wN);
@@ -106,7 +120,7 @@ __global__ void __launch_bounds__(256) k_dist_mid(const uint32_t* recv, uint32_t
   for (int r = 0; r < N; r++) st_packed(out, base + (size_t)r * a.C, x[r]);
 }
 
-// after exchange 3: inverse N-DFT over r, scale g^-k m^-1 (icoset), canonical scalars of
+// after exchange 3: inverse N-DFT over r, scale g^-k m^-1 (icoset), minus c', canonical scalars of
 // h[M t + q] at hbuf[t*C + u], their global index (-1 for k = m-1: truncation, prover.rs:227)
 template <int N>
 __global__ void __launch_bounds__(256) k_dist_final(const uint32_t* recv, uint32_t* hbuf, int32_t* hidx,
@@ -123,7 +137,8 @@ __global__ void __launch_bounds__(256) k_dist_final(const uint32_t* recv, uint32
   for (int t = 0; t < N; t++) {
     const uint32_t k = t * a.M + q;
     DFr v = fe_mul<FrCfg>(x[t], pow_factor(a.sc_lo, a.sc_hi, a.sc_bits, k));
-    v = fe_csub<FrCfg, 1>(fe_from_mont<FrCfg>(v));  // <= r: one subtraction
+    v = fe_sub<FrCfg, 2>(v, ld_packed(a.cprime, (size_t)t * a.C + u));  // v < 2r, c' < 2r: < 4r
+    v = fe_csub<FrCfg, 1>(fe_from_mont<FrCfg>(v));  // v < 2^261, so v * 2^-261 <= r: one subtraction
     uint32_t w[8];
     fe_pack<FrCfg>(v, w);
     uint4* p = reinterpret_cast<uint4*>(hbuf + ((size_t)t * a.C + u) * 8);
@@ -156,6 +171,7 @@ bh_status dist_h_init(bh_ctx* ctx, DistH& d, int N, int rank, int L) {
   BH_TRY_HIP(d.work.alloc(3 * d.M * 32));
   BH_TRY_HIP(d.recv.alloc(3 * d.M * 32));
   BH_TRY_HIP(d.hbuf.alloc(d.M * 32));
+  BH_TRY_HIP(d.cprime.alloc(d.M * 32));
   BH_TRY_HIP(d.hidx.alloc(d.M * 4));
   Domain *D, *Dm;
   bh_status s;
@@ -177,6 +193,8 @@ static bh_status make_args(bh_ctx* ctx, const DistH& d, bool icoset, DistArgs* a
   a->sc_lo = nullptr;
   a->sc_hi = icoset ? D->icoset_full.as<uint32_t>() : D->coset_full.as<uint32_t>();
   a->sc_bits = POW_FULL_TABLE;
+  a->ck = D->consts.as<uint32_t>() + 27;
+  a->cprime = d.cprime.as<uint32_t>();
   // w_N = root_of_unity^(2^(32 - log N))  (the same root as domain.rs:62-66, of order N)
   uint64_t rou_raw[4] = {0x3829971f439f0d2bull, 0xb63683508c2280b9ull, 0xd09b681922c813b4ull, 0x16a2a19edfe81f20ull};
   Fr w = from_int<4>(rou_raw);
@@ -240,11 +258,10 @@ bh_status dist_h_phase3(bh_ctx* ctx, DistH& d, hipStream_t st) {
   if ((s = ctx_domain(ctx, d.L, &D)) || (s = ctx_domain(ctx, d.Lm, &Dm))) return s;
   uint32_t* a = d.recv.as<uint32_t>();
   uint32_t* b = a + d.M * 8;
-  uint32_t* c = b + d.M * 8;
   // coset_fft's local M-point NTTs: DIF (natural q in, bit-reversed j out), omega_M
-  for (uint32_t* x : {a, b, c}) launch_ntt(x, d.Lm, true, Dm->lv_fwd.as<uint32_t>(), nullptr, nullptr, 0, st);
-  // a*b - c, divide_by_z_on_coset (order-agnostic: the three vectors share the layout)
-  launch_pointwise(a, b, c, d.M, 2, D->consts.as<uint32_t>() + 9, st);
+  for (uint32_t* x : {a, b}) launch_ntt(x, d.Lm, true, Dm->lv_fwd.as<uint32_t>(), nullptr, nullptr, 0, st);
+  // a*b, divide_by_z_on_coset (order-agnostic: the two vectors share the layout)
+  launch_pointwise(a, b, nullptr, d.M, 3, D->consts.as<uint32_t>() + 9, st);
   // icoset_fft's local iNTT_M: DIT (bit-reversed j in, natural q out), omega_M^-1
   launch_ntt(a, d.Lm, false, Dm->lv_inv.as<uint32_t>(), nullptr, nullptr, 0, st);
   BH_TRY_HIP(hipGetLastError());
@@ -271,7 +288,7 @@ bh_status dist_h_run(bh_ctx* ctx, DistH& d, const uint32_t* abc_full, const HExc
   if ((s = dist_h_phase1(ctx, d, abc_full, st))) return s;
   if ((s = ex(d.work.as<uint32_t>(), d.recv.as<uint32_t>(), 3, st))) return s;
   if ((s = dist_h_phase2(ctx, d, st))) return s;
-  if ((s = ex(d.work.as<uint32_t>(), d.recv.as<uint32_t>(), 3, st))) return s;
+  if ((s = ex(d.work.as<uint32_t>(), d.recv.as<uint32_t>(), 2, st))) return s;  // a and b: c ended in phase 2
   if ((s = dist_h_phase3(ctx, d, st))) return s;
   if ((s = ex(d.recv.as<uint32_t>(), d.work.as<uint32_t>(), 1, st))) return s;
   return dist_h_final(ctx, d, st);

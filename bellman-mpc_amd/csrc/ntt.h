@@ -10,6 +10,8 @@ namespace bh {
 
 constexpr int POW_FULL_TABLE = -2;
   // post_lo_bits / pow_factor: a full m-entry table in hi
+constexpr int POW_CONST = -1;
+  // post_lo_bits / pow_factor: one constant, hi[0] (9 limbs), for every index
 
 struct FrConst {
   uint32_t v[9];  // raw 29-bit limbs
@@ -17,16 +19,19 @@ struct FrConst {
 
 // What the storing (last) pass of a transform writes, fused into it:
 //   STORE      : the transform, in place (d)
-//   AB_MINUS_C : the transform is c (natural order): pa[i] = (pa[i] * pb[i] - c[i]) * k[0]
-//                (prover.rs:221-225: a*b - c, divide_by_z_on_coset), c itself is not stored
+//   PRODUCT    : the transform is b on the coset: pa[i] = pa[i] * b[i] * k[0] (prover.rs:221-225:
+//                a*b and divide_by_z_on_coset; c is subtracted on the coefficient side, see
+//                `sub`), b itself is not stored
 //   SCALARS    : out[nat] = canonical scalar of element nat for nat < n_out (prover.rs:227-231:
 //                truncate to m-1 and to_le_bits, natural order), the transform is not stored
+// sub (optional, STORE and SCALARS): sub[i] (packed, < 2r, the same position as the element
+// stored) is subtracted after the post-scale, before the element is stored or converted.
 struct NttEpilogue {
-  enum Kind { STORE = 0, AB_MINUS_C = 1, SCALARS = 2 };
+  enum Kind { STORE = 0, PRODUCT = 1, SCALARS = 2 };
   int kind = STORE;
   uint32_t* pa = nullptr;
-  const uint32_t* pb = nullptr;
   const uint32_t* k = nullptr;  // unpacked constant (9 limbs)
+  const uint32_t* sub = nullptr;
   uint32_t* out = nullptr;
   uint32_t n_out = 0;
 };
@@ -36,7 +41,8 @@ struct NttEpilogue {
 // lv: per-level twiddles (9 limbs each) lv[2^v + x] = omega_{2^(v+1)}^x (launch_level_table).
 // post_lo/hi (optional): the stored element with natural index i is multiplied by
 // lo[i & mask] * hi[i >> lo_bits], or by hi[i] with post_lo_bits = POW_FULL_TABLE (one product
-// per element instead of two; the H block's coset / icoset factors, Domain::*_full).
+// per element instead of two; the H block's coset / icoset factors, Domain::*_full), or by the
+// constant hi[0] with post_lo_bits = POW_CONST.
 void launch_ntt(uint32_t* d, int L, bool dif, const uint32_t* lv, const uint32_t* post_lo, const uint32_t* post_hi,
                 int post_lo_bits, hipStream_t st, const uint32_t* src = nullptr,
                 const NttEpilogue& epi = NttEpilogue());
@@ -52,7 +58,7 @@ void launch_scale(uint32_t* a, size_t n, const uint32_t* lo, const uint32_t* hi,
 void launch_table_scale(uint32_t* out, const uint32_t* in, size_t n, const FrConst& k, hipStream_t st);
 // a = a * k - b (packed)
 void launch_scale_sub(uint32_t* a, const uint32_t* b, size_t n, const FrConst& k, hipStream_t st);
-// op 0: a *= b ; 1: a -= b ; 2: a = (a*b - c) * k
+// op 0: a *= b ; 1: a -= b ; 2: a = (a*b - c) * k ; 3: a = a*b*k (c unused)
 void launch_pointwise(uint32_t* a, const uint32_t* b, const uint32_t* c, size_t n, int op, const uint32_t* k,
                       hipStream_t st);
 void launch_fr_convert(const uint32_t* in, uint32_t* out, size_t n, const FrConst& C, int reduce, hipStream_t st);

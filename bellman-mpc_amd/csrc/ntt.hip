@@ -279,19 +279,25 @@ __global__ void __launch_bounds__(NTT_T) k_ntt_pass(uint32_t* data, PassArgs a) 
     for (int l = 0; l < 9; l++) x.v[l] = lds[l * NTT_E + slot];
     const uint32_t nat = DIF ? brev(idx, a.L) : idx;
     if (a.post_hi) x = fe_mul<FrCfg>(x, pow_factor(a.post_lo, a.post_hi, a.post_lo_bits, nat));  // < 2r
-    if (a.epi.kind == NttEpilogue::AB_MINUS_C) {  // x = c (< 22r): pa[idx] = (pa[idx] * pb[idx] - x) * k
-      const DFr p = fe_mul<FrCfg>(ld_packed(a.epi.pa, idx), ld_packed(a.epi.pb, idx));
-      st_packed(a.epi.pa, idx, fe_mul<FrCfg>(fe_sub<FrCfg, 32>(p, x), ld_limbs(a.epi.k, 0)));
+    if (a.epi.kind == NttEpilogue::PRODUCT) {  // x = b (< 22r, normalised limbs): pa[idx] = pa[idx] * x * k
+      // pa < 2r, so pa * x < 44 r^2 < 2^261 r and the Montgomery product ends < 2r
+      const DFr p = fe_mul<FrCfg>(ld_packed(a.epi.pa, idx), x);
+      st_packed(a.epi.pa, idx, fe_mul<FrCfg>(p, ld_limbs(a.epi.k, 0)));
     } else if (a.epi.kind == NttEpilogue::SCALARS) {  // canonical scalar at the natural index
       if (nat < a.epi.n_out) {
+        // x + 2r - sub[idx]: sub < 2r, and x < 2r (post-scaled or a DIF value; < 22r from a bare DIT)
+        if (a.epi.sub) x = fe_sub<FrCfg, 2>(x, ld_packed(a.epi.sub, idx));
         uint32_t w8[8];
-        fe_pack<FrCfg>(fe_csub<FrCfg, 1>(fe_from_mont<FrCfg>(x)), w8);  // x * 2^-261 <= r: one subtraction
+        // x < 24r < 2^261 (< 4r in the H block), so x * 2^-261 <= r: one subtraction
+        fe_pack<FrCfg>(fe_csub<FrCfg, 1>(fe_from_mont<FrCfg>(x)), w8);
         uint4* q = reinterpret_cast<uint4*>(a.epi.out + (size_t)nat * 8);
         q[0] = make_uint4(w8[0], w8[1], w8[2], w8[3]);
         q[1] = make_uint4(w8[4], w8[5], w8[6], w8[7]);
       }
     } else {
       if (!DIF && !a.post_hi) x = fr_qreduce(x);  // a lazily reduced DIT value (< 22r) -> < 2r for the packed form
+      // x < 2r and sub < 2r: x + 2r - sub < 4r, one conditional subtraction back below 2r
+      if (a.epi.sub) x = fe_csub<FrCfg, 2>(fe_sub<FrCfg, 2>(x, ld_packed(a.epi.sub, idx)));
       st_packed(data, idx, x);
     }
   }
@@ -342,7 +348,8 @@ __global__ void __launch_bounds__(256) k_scale_sub(uint32_t* a, const uint32_t* 
   st_packed(a, i, fe_csub<FrCfg, 2>(fe_sub<FrCfg, 2>(x, ld_packed(b, i))));
 }
 
-// op 0: a *= b ; op 1: a -= b ; op 2: out = (a*b - c) * k   (H pipeline, prover.rs:221-225)
+// op 0: a *= b ; op 1: a -= b ; op 2: out = (a*b - c) * k   (H pipeline, prover.rs:221-225) ;
+// op 3: out = a*b*k (the same with c left to the coefficient side, c is not read)
 __global__ void __launch_bounds__(256) k_pointwise(uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t n,
                                                    int op, const uint32_t* k) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -351,6 +358,7 @@ __global__ void __launch_bounds__(256) k_pointwise(uint32_t* a, const uint32_t* 
   DFr r;
   if (op == 0) r = fe_mul<FrCfg>(x, y);
   else if (op == 1) r = fe_csub<FrCfg, 2>(fe_sub<FrCfg, 2>(x, y));
+  else if (op == 3) r = fe_mul<FrCfg>(fe_mul<FrCfg>(x, y), ld_limbs(k, 0));
   else {
     DFr z = ld_packed(c, i);
     r = fe_mul<FrCfg>(fe_sub<FrCfg, 2>(fe_mul<FrCfg>(x, y), z), ld_limbs(k, 0));
@@ -403,9 +411,14 @@ void launch_ntt(uint32_t* d, int L, bool dif, const uint32_t* lv, const uint32_t
     if (src && src != d) hipMemcpyAsync(d, src, 32, hipMemcpyDeviceToDevice, st);
     if (post_hi) hipLaunchKernelGGL(k_scale, dim3(1), dim3(256), 0, st, d, 1u, post_lo, post_hi, post_lo_bits,
                                     (const uint32_t*)nullptr, -1);
-    if (epi.kind == NttEpilogue::AB_MINUS_C)
-      hipLaunchKernelGGL(k_pointwise, dim3(1), dim3(256), 0, st, epi.pa, epi.pb, (const uint32_t*)d, 1u, 2, epi.k);
-    else if (epi.kind == NttEpilogue::SCALARS && epi.n_out)
+    if (epi.kind == NttEpilogue::PRODUCT) {
+      hipLaunchKernelGGL(k_pointwise, dim3(1), dim3(256), 0, st, epi.pa, (const uint32_t*)d, (const uint32_t*)nullptr,
+                         1u, 3, epi.k);
+      return;
+    }
+    if (epi.sub) hipLaunchKernelGGL(k_pointwise, dim3(1), dim3(256), 0, st, d, epi.sub, (const uint32_t*)nullptr, 1u, 1,
+                                    (const uint32_t*)nullptr);
+    if (epi.kind == NttEpilogue::SCALARS && epi.n_out)
       scalars_prepare(d, epi.out, epi.n_out, 2, 0, st);
     return;
   }

@@ -30,10 +30,11 @@ __device__ __forceinline__ uint32_t brev(uint32_t x, int bits) {
   return bits ? (__builtin_bitreverse32(x) >> (32 - bits)) : 0u;
 }
 // factor(i) = lo[i & (2^lo_bits-1)] * hi[i >> lo_bits]   (tables unpacked)
-// lo_bits = POW_FULL_TABLE (ntt.h): hi[i] (a full table); other lo_bits < 0: constant factor hi[0]
+// lo_bits = POW_FULL_TABLE (ntt.h): hi[i] (a full table); POW_CONST: the constant factor hi[0]
+// for every i (one 9-limb entry, no table)
 __device__ __forceinline__ DFr pow_factor(const uint32_t* lo, const uint32_t* hi, int lo_bits, uint32_t i) {
   if (lo_bits == POW_FULL_TABLE) return ld_limbs(hi, i);
-  if (lo_bits < 0) return ld_limbs(hi, 0);
+  if (lo_bits == POW_CONST) return ld_limbs(hi, 0);
   return fe_mul<FrCfg>(ld_limbs(lo, i & ((1u << lo_bits) - 1u)), ld_limbs(hi, i >> lo_bits));
 }
 

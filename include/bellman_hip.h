@@ -207,7 +207,10 @@ bh_status bh_evdom_sync(bh_evdom* d);
 bh_status bh_evdom_free(bh_evdom* d);
 
 /* H block of create_proof: a, b, c hold num_constraints evaluations each (padded to m
- * internally); h_out receives m-1 Montgomery coefficients; *h_len = m-1. */
+ * internally); h_out receives m-1 Montgomery coefficients; *h_len = m-1.  Six transforms
+ * instead of the reference's seven, the same h for every input: a and b take ifft +
+ * coset_fft, c its ifft alone, h = icoset_fft(a*b / Z) - ifft(c) / Z (c has degree < m, so
+ * icoset_fft undoes its coset_fft; icoset_fft is linear). */
 bh_status bh_compute_h(bh_ctx* ctx, const uint64_t* a, const uint64_t* b, const uint64_t* c,
                        size_t num_constraints, uint64_t* h_out, size_t* h_len);
 
