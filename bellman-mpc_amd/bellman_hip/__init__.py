@@ -62,7 +62,12 @@ class AssignmentMissing(SynthesisError):
         super().__init__(6, "assignment missing")
 
 
-_ERRS = {1: UnexpectedIdentity, 2: UnexpectedEof, 3: PolynomialDegreeTooLarge, 4: DensitySizeMismatch}
+class UnconstrainedVariable(SynthesisError):
+    pass
+
+
+_ERRS = {1: UnexpectedIdentity, 2: UnexpectedEof, 3: PolynomialDegreeTooLarge, 4: DensitySizeMismatch,
+         5: UnconstrainedVariable}
 
 
 def _load():
@@ -156,6 +161,12 @@ def _load():
         "bh_evdom_into_scalars": (I, [P, S, P]),
         "bh_evdom_sync": (I, [P]),
         "bh_evdom_free": (I, [P]),
+        "bh_r1cs_create": (I, [P, S, S, S, P, P, P, P, P, P, P, P, P, P]),
+        "bh_r1cs_free": (I, [P]),
+        "bh_r1cs_sizes": (I, [P, P]),
+        "bh_r1cs_eval": (I, [P, P, P, P, P, P]),
+        "bh_generate_parameters": (I, [P, P, P, P, P, P, P, P]),
+        "bh_chain_r1cs": (I, [P, S, U64, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -185,7 +196,8 @@ EXPORTED_SYMBOLS = [
     "bh_evdom_from_coeffs", "bh_evdom_size", "bh_evdom_fft", "bh_evdom_ifft", "bh_evdom_coset_fft",
     "bh_evdom_icoset_fft", "bh_evdom_distribute_powers", "bh_evdom_divide_by_z_on_coset", "bh_evdom_mul_assign",
     "bh_evdom_sub_assign", "bh_evdom_read", "bh_evdom_write", "bh_evdom_into_scalars", "bh_evdom_sync",
-    "bh_evdom_free",
+    "bh_evdom_free", "bh_r1cs_create", "bh_r1cs_free", "bh_r1cs_sizes", "bh_r1cs_eval", "bh_generate_parameters",
+    "bh_chain_r1cs",
 ]
 BH_VEC_H, BH_VEC_L, BH_VEC_A, BH_VEC_B_G1, BH_VEC_B_G2 = range(5)
 PARTIAL_BYTES = 960
@@ -225,6 +237,14 @@ def fr_from_mont(arr):
         x = sum(int(row[k]) << (64 * k) for k in range(4))
         out.append(x * _MONT_RINV % R_MODULUS)
     return out
+
+
+def fr_canonical_words(x):
+    """One int in [0, 2^256) -> 4 LE uint64 words, NOT reduced (the library rejects words >= r)."""
+    x = int(x)
+    if not 0 <= x < 1 << 256:
+        raise ValueError("not a 256-bit value")
+    return np.array([(x >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)], dtype=np.uint64)
 
 
 def fr_to_canonical_limbs(values):
@@ -711,6 +731,16 @@ class Parameters:
                "bh_chain_params")
         return cls(ctx, h)
 
+    @classmethod
+    def generate(cls, ctx, r1cs, alpha=6, beta=24, gamma=6, delta=24, tau=2):
+        """generate_parameters (generator.rs:241-634) on a device-resident R1CS; the toxic waste as
+        ints below r (the defaults are the fork's, generator.rs:21-40)."""
+        w = [fr_canonical_words(x) for x in (alpha, beta, gamma, delta, tau)]
+        h = ctypes.c_void_p()
+        _check(_lib.bh_generate_parameters(ctx.h, r1cs.h, *[_ptr(x) for x in w], ctypes.byref(h)),
+               "bh_generate_parameters")
+        return cls(ctx, h)
+
     def sizes(self):
         out = (ctypes.c_size_t * 6)()
         _check(_lib.bh_params_sizes(self.h, out))
@@ -791,6 +821,139 @@ class LinearCombination:
         if isinstance(x, LinearCombination):
             return LinearCombination(self.terms + [(v, -c * coeff) for v, c in x.terms])
         return LinearCombination(self.terms + [(x, -coeff)])
+
+
+# ------------------------------------------------------------------ parameter generation (generator.rs)
+class KeypairAssembly:
+    """generator.rs:44-156: per variable, the (coeff mod r, constraint) terms of A, B and C."""
+
+    def __init__(self):
+        self.num_inputs = self.num_aux = self.num_constraints = 0
+        self.at_inputs, self.bt_inputs, self.ct_inputs = [], [], []
+        self.at_aux, self.bt_aux, self.ct_aux = [], [], []
+
+    @staticmethod
+    def one():
+        return ONE
+
+    def namespace(self, name):
+        return self
+
+    def alloc(self, name, f):
+        self.num_aux += 1
+        for t in (self.at_aux, self.bt_aux, self.ct_aux):
+            t.append([])
+        return Variable("aux", self.num_aux - 1)
+
+    def alloc_input(self, name, f):
+        self.num_inputs += 1
+        for t in (self.at_inputs, self.bt_inputs, self.ct_inputs):
+            t.append([])
+        return Variable("input", self.num_inputs - 1)
+
+    def enforce(self, name, la, lb, lc):
+        z = LinearCombination.zero
+        for lcx, ins, auxs in ((la(z()), self.at_inputs, self.at_aux), (lb(z()), self.bt_inputs, self.bt_aux),
+                               (lc(z()), self.ct_inputs, self.ct_aux)):
+            for var, coeff in lcx.terms:
+                (ins if var.kind == "input" else auxs)[var.index].append((int(coeff) % R_MODULUS,
+                                                                          self.num_constraints))
+        self.num_constraints += 1
+
+    def matrices(self):
+        """The three matrices in bh_r1cs_create's layout: [(ptr u64 (n+1), row u32 (nnz), coeff
+        (nnz,4) u64 Montgomery)] for A, B, C over the variables [inputs, then aux]."""
+        return [flatten_columns(i + a) for i, a in ((self.at_inputs, self.at_aux), (self.bt_inputs, self.bt_aux),
+                                                    (self.ct_inputs, self.ct_aux))]
+
+
+def flatten_columns(columns):
+    """Per-variable [(coeff, row)] lists -> (ptr, row, coeff) arrays of bh_r1cs_create."""
+    ptr = np.zeros(len(columns) + 1, dtype=np.uint64)
+    ptr[1:] = np.cumsum([len(c) for c in columns], dtype=np.uint64) if columns else []
+    row = np.array([r for c in columns for _, r in c], dtype=np.uint32)
+    coeff = fr_to_mont([k for c in columns for k, _ in c])
+    return ptr, row, coeff
+
+
+def unflatten_columns(ptr, row, coeff):
+    """Inverse of flatten_columns (coefficients back as ints mod r)."""
+    ks = fr_from_mont(coeff)
+    return [[(ks[t], int(row[t])) for t in range(int(ptr[j]), int(ptr[j + 1]))] for j in range(len(ptr) - 1)]
+
+
+class R1CS:
+    """A KeypairAssembly resident in HBM (bh_r1cs)."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    @classmethod
+    def from_arrays(cls, ctx, num_inputs, num_aux, num_constraints, a, b, c):
+        """a, b, c: (ptr, row, coeff) as flatten_columns returns them."""
+        h = ctypes.c_void_p()
+        args = []
+        for ptr, row, coeff in (a, b, c):
+            args += [None if ptr is None else np.ascontiguousarray(ptr, dtype=np.uint64),
+                     None if row is None else np.ascontiguousarray(row, dtype=np.uint32),
+                     None if coeff is None else np.ascontiguousarray(coeff, dtype=np.uint64)]
+        _check(_lib.bh_r1cs_create(ctx.h, num_inputs, num_aux, num_constraints, *[_ptr(x) for x in args],
+                                   ctypes.byref(h)), "bh_r1cs_create")
+        return cls(ctx, h)
+
+    @classmethod
+    def from_assembly(cls, ctx, asm):
+        return cls.from_arrays(ctx, asm.num_inputs, asm.num_aux, asm.num_constraints, *asm.matrices())
+
+    @classmethod
+    def chain(cls, ctx, rounds, seed=7):
+        h = ctypes.c_void_p()
+        _check(_lib.bh_chain_r1cs(ctx.h, rounds, seed, ctypes.byref(h)), "bh_chain_r1cs")
+        return cls(ctx, h)
+
+    def sizes(self):
+        out = (ctypes.c_size_t * 7)()
+        _check(_lib.bh_r1cs_sizes(self.h, out))
+        return dict(zip(["inputs", "aux", "constraints", "nnz_a", "nnz_b", "nnz_c", "segment"], list(out)))
+
+    def eval(self, x):
+        """x: m ints (m = the domain size of the constraint count) -> (u, v, w), one int per
+        variable each (eval_at_tau of generator.rs:485-499 for A, B, C)."""
+        sz = self.sizes()
+        n = sz["inputs"] + sz["aux"]
+        m = ctypes.c_size_t()
+        _check(_lib.bh_domain_size(sz["constraints"], ctypes.byref(m), None))
+        if len(x) != m.value:
+            raise ValueError(f"x must have {m.value} entries")
+        xm = fr_to_mont(x)
+        outs = [np.zeros((n, 4), dtype=np.uint64) for _ in range(3)]
+        _check(_lib.bh_r1cs_eval(self.ctx.h, self.h, _ptr(xm), *[_ptr(o) for o in outs]), "bh_r1cs_eval")
+        return tuple(fr_from_mont(o) for o in outs)
+
+    def __del__(self):
+        try:
+            _lib.bh_r1cs_free(self.h)
+        except Exception:
+            pass
+
+
+def synthesize_keypair(circuit):
+    """generator.rs:262-274: ONE, then the circuit (the input rows are appended by the library)."""
+    asm = KeypairAssembly()
+    asm.alloc_input("", lambda: 1)
+    circuit.synthesize(asm)
+    return asm
+
+
+def generate_parameters(ctx, circuit, alpha, beta, gamma, delta, tau):
+    """generator.rs:241-634 (classic algorithm): synthesize on the host, generate on the device."""
+    r1cs = R1CS.from_assembly(ctx, synthesize_keypair(circuit))
+    return Parameters.generate(ctx, r1cs, alpha, beta, gamma, delta, tau)
+
+
+def generate_random_parameters(ctx, circuit, rng=None):
+    """generator.rs:21-40: the fork ignores rng and uses alpha=6, beta=24, gamma=6, delta=24, tau=2."""
+    return generate_parameters(ctx, circuit, 6, 24, 6, 24, 2)
 
 
 class DensityTracker:

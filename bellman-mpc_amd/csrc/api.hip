@@ -617,6 +617,11 @@ static bh_status run_fft(bh_ctx* ctx, Domain* D, FftKind kind, uint32_t* d_a, ui
   return BH_OK;
 }
 
+// the resident ifft for callers outside this file (r1cs.h)
+bh_status device_ifft(bh_ctx* ctx, Domain* D, uint32_t* d_a, uint32_t* d_tmp) {
+  return run_fft(ctx, D, IFFT, d_a, d_tmp);
+}
+
 static bh_status host_fft(bh_ctx* ctx, uint64_t* coeffs, uint32_t log_m, FftKind kind) {
   if (!ctx || !coeffs || log_m >= 32) return BH_ERR_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(ctx->mu);

@@ -19,6 +19,7 @@
 
 #include "api_internal.h"
 #include "crs.h"
+#include "r1cs.h"
 
 using namespace bh;
 
@@ -254,6 +255,14 @@ bh_status fixed_base_to_srs(bh_ctx* ctx, const std::vector<AffinePt<T>>& table, 
 }
 
 }  // namespace
+
+// the generators and fixed-base tables for the general generator (r1cs.hip)
+namespace bh {
+Jac<Fp> crs_g1_gen() { return g1_gen(); }
+Jac<Fp2> crs_g2_gen() { return g2_gen(); }
+std::vector<AffinePt<Fp>> crs_table_g1() { return fixed_base_table<Fp>(g1_gen()); }
+std::vector<AffinePt<Fp2>> crs_table_g2() { return fixed_base_table<Fp2>(g2_gen()); }
+}  // namespace bh
 
 // ---------------------------------------------------------------- fused chain synthesis
 // MiMCDemo::synthesize (mimc_mod.rs:50-129) fused with the ProvingAssignment it feeds
@@ -528,6 +537,35 @@ bh_status bh_chain_params(bh_ctx* ctx, size_t rounds, uint64_t seed, uint64_t al
   p->delta_g2 = g2mul(delta);
   *out = p.release();
   return BH_OK;
+}
+
+// the KeypairAssembly bh_chain_params synthesizes, flattened into bh_r1cs_create's arrays (the
+// input rows are left to the library, as generate_parameters appends them after synthesize)
+bh_status bh_chain_r1cs(bh_ctx* ctx, size_t rounds, uint64_t seed, bh_r1cs** out) {
+  if (!ctx || !out || rounds == 0) return BH_ERR_INVALID_ARGUMENT;
+  const std::vector<Fr> consts = fr_stream(seed, rounds);
+  KeypairAssemblyN asm_;
+  synthesize_chain(asm_, consts, Fr::zero(), Fr::zero());
+  const size_t ni = asm_.at_in.size(), na = asm_.at_aux.size(), n = ni + na;
+  std::vector<uint64_t> ptr[3], coeff[3];
+  std::vector<uint32_t> row[3];
+  const std::vector<std::vector<KeypairAssemblyN::Entry>>* mats[3][2] = {
+      {&asm_.at_in, &asm_.at_aux}, {&asm_.bt_in, &asm_.bt_aux}, {&asm_.ct_in, &asm_.ct_aux}};
+  for (int k = 0; k < 3; k++) {
+    ptr[k].reserve(n + 1);
+    ptr[k].push_back(0);
+    for (int half = 0; half < 2; half++)
+      for (const auto& col : *mats[k][half]) {
+        for (const auto& e : col) {
+          row[k].push_back(e.row);
+          coeff[k].insert(coeff[k].end(), e.coeff.v, e.coeff.v + 4);
+        }
+        ptr[k].push_back(row[k].size());
+      }
+  }
+  return bh_r1cs_create(ctx, ni, na, asm_.num_constraints, ptr[0].data(), row[0].data(), coeff[0].data(),
+                        ptr[1].data(), row[1].data(), coeff[1].data(), ptr[2].data(), row[2].data(),
+                        coeff[2].data(), out);
 }
 
 }  // extern "C"

@@ -1,0 +1,43 @@
+// Internal interface of the device-resident KeypairAssembly (r1cs.hip) and what it borrows from
+// the chain generator (chain.hip) and the NTT plumbing (api.hip).
+#pragma once
+#include <vector>
+
+#include "api_internal.h"
+#include "kinfo.h"
+
+// KeypairAssembly in HBM (generator.rs:44-156): the term lists of A, B and C concatenated in the
+// column order [A inputs, A aux, B inputs, B aux, C inputs, C aux] (3 * (ni + na) columns), every
+// column cut into segments of at most bh::R1CS_S terms.  Segments tile the term array in order, so
+// seg[k] .. seg[k + 1] is segment k and colseg[j] .. colseg[j + 1] are column j's segments.
+struct bh_r1cs {
+  int device = 0;
+  size_t ni = 0, na = 0;
+  size_t nc = 0;            // constraints including the ni appended rows input_i * 0 = 0
+  size_t m = 0;             // domain size of nc
+  uint32_t L = 0;
+  size_t nnz[3] = {0, 0, 0};  // A (with the appended terms), B, C
+  size_t terms = 0, nseg = 0, ncol = 0, nlong = 0;
+  bh::DevBuf coeff;         // terms x 8 u32, packed device Montgomery
+  bh::DevBuf row;           // terms u32
+  bh::DevBuf seg;           // nseg + 1 u32: first term of each segment, seg[nseg] = terms
+  bh::DevBuf colseg;        // ncol + 1 u32: first segment of each column
+  bh::DevBuf longcols;      // nlong u32: the columns with more than R1CS_S segments
+};
+
+namespace bh {
+// terms per segment = the dependent Fr products one lane of the QAP kernel runs at most
+constexpr uint32_t R1CS_S = 32;
+
+void r1cs_kernels(std::vector<KernInfo>& v);  // scratch budget (scratch.cpp)
+
+// chain.hip: the generators and their 32 x 255 fixed-base window tables (crs.hip's layout)
+Jac<Fp> crs_g1_gen();
+Jac<Fp2> crs_g2_gen();
+std::vector<AffinePt<Fp>> crs_table_g1();
+std::vector<AffinePt<Fp2>> crs_table_g2();
+
+// api.hip: the ifft (domain.rs:104-121) of 2^L packed device-Montgomery Fr resident in d_a, natural
+// order in and out, d_tmp the same size; enqueued on ctx->stream (caller holds ctx->mu)
+bh_status device_ifft(bh_ctx* ctx, Domain* D, uint32_t* d_a, uint32_t* d_tmp);
+}  // namespace bh

@@ -19,6 +19,8 @@
  *   bh_params_*            Parameters / ParameterSource  groth16/mod.rs:224-477
  *   bh_prove / bh_prove_witness
  *                          create_proof after synthesis   groth16/prover.rs:206-349
+ *   bh_r1cs_*              KeypairAssembly                groth16/generator.rs:44-156
+ *   bh_generate_parameters generate_parameters            groth16/generator.rs:241-634
  *
  * Conventions
  *   - Plain pointers and sizes only; the caller owns every host buffer and the
@@ -356,6 +358,56 @@ bh_status bh_chain_assignment(size_t rounds, uint64_t seed, uint64_t preimage_se
                               uint64_t* b_input_density, uint64_t* b_aux_density);
 bh_status bh_chain_params(bh_ctx* ctx, size_t rounds, uint64_t seed, uint64_t alpha, uint64_t beta, uint64_t gamma,
                           uint64_t delta, uint64_t tau, bh_params** out);
+
+/* ---- parameter generation for any circuit: KeypairAssembly (generator.rs:44-156) resident in
+ * HBM, and the classic generate_parameters (generator.rs:241-634, without the fork's MPC asserts)
+ * on it. */
+typedef struct bh_r1cs bh_r1cs;
+
+/* KeypairAssembly's at_inputs .. ct_aux (generator.rs:44-60) as three column-compressed matrices,
+ * one each for A, B, C, over the variables in the order [inputs (input 0 is ONE), then aux].  For
+ * variable j, entries [ptr[j], ptr[j+1]) are (coeff: Montgomery Fr, 4 u64; row: constraint index,
+ * u32) in the order enforce (generator.rs:113-151) appended them.  Duplicates of a (variable, row)
+ * pair are allowed and add up.  ptr has num_inputs + num_aux + 1 u64 entries; row and coeff may be
+ * null where a matrix has no entry.
+ * num_constraints counts the circuit's own constraints only: the library appends the num_inputs
+ * rows "input_i * 0 = 0" itself (generator.rs:276-282), as generate_parameters does after
+ * synthesize.
+ * BH_ERR_INVALID_ARGUMENT: a null pointer, num_inputs == 0, a ptr that does not start at 0 or
+ * decreases, a row >= num_constraints, a coefficient >= r (all checked before anything is indexed),
+ * or more than 2^32 - 1 terms in all or (2^32 - 1) / 3 variables (the device offsets are u32).
+ * BH_ERR_POLY_DEGREE_TOO_LARGE: num_constraints + num_inputs exceeds the largest domain
+ * (generator.rs:284-288 via domain.rs:51-60). */
+bh_status bh_r1cs_create(bh_ctx* ctx, size_t num_inputs, size_t num_aux, size_t num_constraints,
+                         const uint64_t* a_ptr, const uint32_t* a_row, const uint64_t* a_coeff,
+                         const uint64_t* b_ptr, const uint32_t* b_row, const uint64_t* b_coeff,
+                         const uint64_t* c_ptr, const uint32_t* c_row, const uint64_t* c_coeff,
+                         bh_r1cs** out);
+bh_status bh_r1cs_free(bh_r1cs* r);
+/* out[0..7): inputs, aux, constraints including the appended input rows, terms of A (including
+ * the appended ones), of B, of C, and the segment length S: the most terms one lane of the QAP
+ * kernel multiplies. */
+bh_status bh_r1cs_sizes(const bh_r1cs* r, size_t out[7]);
+/* eval_at_tau (generator.rs:485-499) for every variable at once.  x: m Montgomery Fr, m the domain
+ * size of the constraint count (the Lagrange coefficients, or any vector).  u_out, v_out, w_out
+ * receive num_inputs + num_aux Montgomery Fr each: u_j = sum over column j of A of coeff * x[row],
+ * likewise v (B) and w (C); an empty column gives 0. */
+bh_status bh_r1cs_eval(bh_ctx* ctx, const bh_r1cs* r, const uint64_t* x, uint64_t* u_out, uint64_t* v_out,
+                       uint64_t* w_out);
+/* generate_parameters (generator.rs:241-634, the classic algorithm of generator.rs:310-572 and the
+ * identity filter of 614-633).  Toxic waste as canonical Fr (4 LE u64 each, full width; a word
+ * >= r: BH_ERR_INVALID_ARGUMENT).  gamma or delta zero: BH_ERR_UNEXPECTED_IDENTITY
+ * (generator.rs:330-345).  An aux variable whose L scalar is zero: BH_ERR_UNCONSTRAINED_VARIABLE
+ * (generator.rs:586-590).  An ic scalar that is zero is legal and encodes the identity.
+ * The one deliberate deviation: tau = 0 or tau^m = 1 returns BH_ERR_INVALID_ARGUMENT, where the
+ * reference would write identity points into the h query.
+ * The result is an ordinary bh_params. */
+bh_status bh_generate_parameters(bh_ctx* ctx, const bh_r1cs* r, const uint64_t alpha[4], const uint64_t beta[4],
+                                 const uint64_t gamma[4], const uint64_t delta[4], const uint64_t tau[4],
+                                 bh_params** out);
+/* The MiMC chain's KeypairAssembly (what bh_chain_params synthesizes internally) as a bh_r1cs. */
+bh_status bh_chain_r1cs(bh_ctx* ctx, size_t rounds, uint64_t seed, bh_r1cs** out);
+
 /* Parameters::write of device-resident params (for parity tests; host copy). */
 bh_status bh_params_write(const bh_params* p, uint8_t* out, size_t cap, size_t* written);
 
