@@ -8,6 +8,7 @@
 
 #include "curve.cuh"
 #include "kinfo.h"
+#include "msm_rowcol.h"
 
 namespace bh {
 
@@ -20,7 +21,6 @@ struct MsmShape {
   int c;    // window bits
   int W;    // digit windows = ceil(256 / c) (signed digits need one spare bit)
   int NB;   // buckets per bucket window = 2^(c-1)
-  int L;    // buckets per running-sum thread
   int S;    // sorted entries per accumulation thread
   int Wb;   // bucket windows: W, or 1 with a window table (all windows share the buckets)
   int pre;  // 1: bases are a window table T[i*W + w] = 2^(c*w) * P_i (entry = i*W + w)
@@ -37,52 +37,36 @@ struct MsmShape {
 };
 // a bucket shard's bounds are multiples of this: every partition of the digit sort (<= 128
 // buckets at the table window sizes) lies in one rank's range, and the range is a whole number
-// of k_reduce_blocks blocks (L * BT divides it: L <= 4 for G1's 256 threads, <= 8 for G2's 128)
+// of rows of the row/column reduction (Cn <= 1024 columns, msm_rowcol.h)
 constexpr uint32_t BUCKET_SHARD_GRANULE = 1024;
 MsmShape msm_shape(size_t n, int c_override);
 // shape for a window table: c from the cost model n*ceil(256/c) + ~6.5 * 2^(c-1)
 int msm_table_c(size_t n);
 MsmShape msm_shape_table(size_t n, int c);
 
-// Bucket-reduction geometry (msm_back): L buckets per level-1 thread, blocks of
-// reduce_block_threads() threads.  With a single bucket window (Wb == 1) the device returns
-// two points and the host finishes the window: out[0] + 2^reduce_split_shift() * out[1]
-// (the shift's doublings are a serial chain: cheaper on the host than on one device thread).
-uint32_t reduce_block_max(bool g2);  // 256 (G1) / 128 (G2) threads (64 and 128 were slower)
-// (for a bucket range of nbr buckets, L per thread)
-inline uint32_t reduce_threads_for(uint32_t nbr, uint32_t L, bool g2) {
-  const uint32_t T = nbr / L, bmax = reduce_block_max(g2);
-  return T < bmax ? T : bmax;
-}
-inline uint32_t reduce_block_threads(const MsmShape& sh, bool g2) {
-  return reduce_threads_for((uint32_t)sh.NB, (uint32_t)sh.L, g2);
-}
+// Bucket-reduction geometry (msm_back): the row/column sums of msm_rowcol.h.  For one shared
+// bucket window (Wb == 1, the window tables) the device returns out[0] = sum_j (j+1) Col_j,
+// out[1] = sum_k k Row_k (and a shard's out[2] = sum_k Row_k) and the host finishes the window:
+// out[0] + 2^reduce_split_shift() * out[1] (the shift's doublings are a serial chain: cheaper on
+// the host than on one device thread).  For several windows (plain multiexps) it returns one
+// total per window.
+uint32_t reduce_block_max(bool g2);  // k_rowcol_final: 256 (G1) / 128 (G2) threads
 inline int reduce_lg2(uint32_t x) {
   int r = 0;
   while ((1u << r) < x) r++;
   return r;
 }
-inline int reduce_shift_for(uint32_t nbr, uint32_t L, bool g2) {
-  return reduce_lg2(L) + reduce_lg2(reduce_threads_for(nbr, L, g2));
-}
 inline int reduce_split_shift(const MsmShape& sh, bool g2) {
-  return sh.Wb == 1 ? reduce_shift_for(sh.red_nb(), (uint32_t)sh.L, g2) : -1;
+  return sh.Wb == 1 ? rowcol_geom(sh.red_nb(), ROWCOL_QLG, g2).lc : -1;
+}
+// points of each of the two partial arrays (seg_weighted, seg_sum) the reduction of `sh` needs
+inline size_t reduce_partial_points(const MsmShape& sh, bool g2) {
+  const RowColGeom g = rowcol_geom(sh.red_nb(), ROWCOL_QLG, g2);
+  return (size_t)sh.Wb * (g.col_points > g.row_points ? g.col_points : g.row_points);
 }
 // A bucket shard's device result is out[0] + 2^reduce_split_shift * out[1] + bk_lo * out[2]
 // (combine_g1 / combine_g2; out[2] = the plain sum of the range's buckets, each of which holds
 // digit bk_lo more than its position in the range).
-// Level-2 geometry of the bucket reduction over nblk level-1 blocks: BT2 threads (a power of two)
-// of Lb blocks each (a power of two), BT2 * Lb >= nblk (blocks past nblk read as identities)
-inline void reduce_level2(uint32_t nblk, bool g2, uint32_t* BT2, uint32_t* Lb) {
-  const uint32_t bmax = g2 ? 128u : 256u;
-  uint32_t lb = 1;
-  while ((size_t)bmax * lb < nblk) lb <<= 1;
-  uint32_t t = 1;
-  while ((size_t)t * lb < nblk) t <<= 1;
-  *BT2 = t;
-  *Lb = lb;
-}
-
 struct MsmTiming {
   hipEvent_t ev_acc_begin = nullptr, ev_acc_end = nullptr;  // bracket k_accumulate_dev
 };
@@ -154,7 +138,6 @@ template <class C>
 void msm_acc_kernels(std::vector<KernInfo>& v);
 template <class C>
 void msm_back_kernels(std::vector<KernInfo>& v);
-size_t reduce_blocks_resident_per_cu_g1();  // (msm_g1_back.hip)
 // max over buckets of (last segment - first segment) for segment length S: the
 // continuation-tree depth msm_back needs.  Each of max_span_blocks(nbt) workgroups writes its
 // own maximum to d_words[b] and the (pinned) h_words receive them, stream-ordered; the host takes

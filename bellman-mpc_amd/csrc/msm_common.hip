@@ -15,10 +15,9 @@
 //               mixed XYZZ additions of the gathered affine bases; perfectly
 //               load balanced whatever the digit distribution.  Partial sums
 //               of buckets that straddle segments go to a per-segment slot.
-//   k_bucket_reduce one thread per L consecutive buckets: running sums
-//               (summation by parts) -> (sum_t, weighted_t)
-//   k_seg_combine  weighted_t + (t*L)*sum_t
-//   k_sum_groups   per-window sum of the segment results, a 4-ary tree of launches
+//   k_cont_fold / k_rowcol_sum / k_rowcol_final  the buckets of a window as rows x columns:
+//               plain row and column sums by levels, then two short weighted sums
+//               (msm_rowcol.h) -> one total per window
 // The host then performs the W-window Horner step (multiexp.rs:244-249).
 //
 // Semantics of the reference Source (multiexp.rs:45-86) are reproduced by the
@@ -216,9 +215,6 @@ __device__ __forceinline__ void load_scalar(const uint32_t* scalars, size_t i, u
 // {c-1, c, c+1} whose top window is fullest (a nearly empty top window piles
 // every scalar into a handful of giant buckets).  Segment length S keeps about
 // 2^18 accumulation threads in flight.  Results never depend on either choice.
-// minimum bucket-reduction threads: a small bucket set's tail is latency-bound
-static constexpr size_t REDUCE_T_MIN = 16384;
-
 MsmShape msm_shape(size_t n, int c_override) {
   MsmShape sh;
   int c = c_override;
@@ -238,13 +234,6 @@ MsmShape msm_shape(size_t n, int c_override) {
   sh.c = c;
   sh.W = (256 + c - 1) / c;
   sh.NB = 1 << (c - 1);
-  // buckets per reduction thread (msm_back): up to 8 (~3 additions per bucket; 16 would do less
-  // work, but its longer-lived waves cost the overlapped accumulations more: +2 ms per 2^22
-  // proof in a same-box A/B), fewer when that leaves under 16384 threads (a small bucket set's
-  // tail is latency-bound: a shard's G2 tail at 2^15 buckets took 5.8 ms beside the
-  // accumulations with L = 8, 4096 threads)
-  sh.L = std::min<int>(8, sh.NB);
-  while (sh.L > 1 && (size_t)sh.W * (size_t)(sh.NB / sh.L) < REDUCE_T_MIN) sh.L >>= 1;
   size_t E = n * (size_t)sh.W;
   int S = 16;
   while (S < 256 && E / (size_t)(2 * S) >= ((size_t)1 << 18)) S <<= 1;
@@ -257,10 +246,12 @@ MsmShape msm_shape(size_t n, int c_override) {
 
 // With a window table every digit window adds into one shared set of 2^(c-1) buckets, so
 // the accumulation costs n*ceil(256/c) mixed additions and the reduction ~6.5 * 2^(c-1)
-// mixed-addition equivalents, independent of W.  The reduction does ~3 full additions per bucket
-// (msm_back), but beside the accumulations its latency-bound waves cost about twice their
-// instructions: measured at 2^20 points, c = 16 beats c = 20 by 0.5 ms per proof (a weight of
-// 3.6 picked c = 20 there); c = 20 stays the choice at 2^22.
+// mixed-addition equivalents, independent of W.  The weight was fitted to the earlier reduction
+// (a running-sum kernel with a block epilogue, ~5 full additions per bucket, whose latency-bound
+// waves cost about twice their instructions beside the accumulations: measured at 2^20 points,
+// c = 16 beat c = 20 by 0.5 ms per proof where a weight of 3.6 picked c = 20).  The row/column
+// sums do ~2 additions per bucket plus one per continuation partial; the weight
+// has not been refitted for them, and c = 20 stays the choice at 2^22 under any weight from 3 to 13.
 // Only window sizes whose top window holds >= 10 real scalar bits: with shared buckets a
 // nearly empty top window (e.g. c = 17: the 16th window only takes the carry; c = 18: 3 bits)
 // pours up to n/2 entries into a handful of small-digit buckets, whose continuation partials
@@ -292,8 +283,6 @@ MsmShape msm_shape_table(size_t n, int c) {
   MsmShape sh = msm_shape(n, c);
   sh.Wb = 1;
   sh.pre = 1;
-  // one shared bucket window: the reduction's thread count is NB / L
-  while (sh.L > 1 && (size_t)(sh.NB / sh.L) < REDUCE_T_MIN) sh.L >>= 1;
   return sh;
 }
 
@@ -585,3 +574,23 @@ hipError_t density_index(const uint64_t* d_words, size_t n, uint32_t base_offset
 }
 
 }  // namespace bh
+
+// The row/column reduction's geometry as words, for the host test of the identity
+// (tests/test_bucket_rowcol_cpu.py; not part of the public header): lc, Cn, R, ncol, nrow,
+// final_threads, final_per_thread, col_points, row_points, then rows_in, rows_out, inner, Q,
+// out_off of every column level and of every row level.  Returns the words written, -1 if cap
+// is too small.
+extern "C" int bh_selftest_rowcol_geometry(uint32_t nbr, int qlg, int g2, uint64_t* out, size_t cap) {
+  const bh::RowColGeom g = bh::rowcol_geom(nbr, qlg, g2 != 0);
+  const size_t need = 9 + 5 * (size_t)(g.ncol + g.nrow);
+  if (!out || cap < need) return -1;
+  size_t k = 0;
+  out[k++] = (uint64_t)g.lc; out[k++] = g.Cn; out[k++] = g.R; out[k++] = (uint64_t)g.ncol; out[k++] = (uint64_t)g.nrow;
+  out[k++] = g.final_threads; out[k++] = g.final_per_thread; out[k++] = g.col_points; out[k++] = g.row_points;
+  for (int r = 0; r < 2; r++)
+    for (int i = 0; i < (r ? g.nrow : g.ncol); i++) {
+      const bh::RowColLevel& l = r ? g.row[i] : g.col[i];
+      out[k++] = l.rows_in; out[k++] = l.rows_out; out[k++] = l.inner; out[k++] = l.Q; out[k++] = l.out_off;
+    }
+  return (int)k;
+}

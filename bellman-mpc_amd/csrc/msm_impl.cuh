@@ -111,7 +111,7 @@ __device__ __forceinline__ uint32_t block_span(const uint32_t* words, uint32_t g
 // segments costs 4 + 2 serial additions instead of 15.  The tails are VALU-bound chains
 // on a small fraction of the SIMDs: serial depth is their latency.
 // span_words != null (device-decided): the whole grid returns when the longest span is at most
-// fold_span (k_reduce_blocks folds those), and otherwise folds every bucket spanning at most
+// fold_span (k_cont_fold adds those), and otherwise folds every bucket spanning at most
 // seq_max segments; longer ones are k_cont_long's (a serial chain over thousands of partials
 // would be the tail's latency: a witness full of ones puts most entries in one bucket).
 template <class C, int Q>
@@ -211,20 +211,13 @@ __global__ void __launch_bounds__(256) k_cont_long(const uint32_t* counts, const
 }
 
 // ---- Bucket reduction: window total  sum_{b < NB} (b+1) * B_b  (bucket b holds digit b+1;
-// multiexp.rs:225-235 computes it as one serial running sum per window).  Here it is a
-// two-level summation by parts with no scalar multiplications of partial sums:
-//   thread t of block `blk` (t = blk*BT + i) owns buckets [t*L, t*L + L):
-//     R_t = sum_k B,  A_t = sum_k (k+1) B          (2L additions, the running-sum idiom)
-//   then  sum_b (b+1) B_b = sum_t A_t + L * sum_t t R_t,  and inside a block
-//     sum_i (t0 + i) R = t0 * S_blk + sum_i V_i,   V_i = sum_{j > i} R_j (LDS suffix scan)
-//   so block blk emits Y_blk = sum_i (A_i + L*V_i) and S_blk = sum_i R_i, and
-//     window total = sum_blk Y_blk + (L*BT) * sum_blk blk * S_blk,
-//   the same shape one level up (k_reduce_window, one block per window).
-// Work ~ (2 + (log2 BT + log2 L) / L) additions per bucket; serial depth 2L + 2 log2 BT + log2 L.
+// multiexp.rs:225-235 computes it as one serial running sum per window).  Here: the row and
+// column sums of msm_rowcol.h (k_cont_fold, k_rowcol_sum, k_rowcol_final below), with no scalar
+// multiplications of partial sums.
 //
-// Each kernel is written as short programs of point operations with ONE addition and one
-// doubling call site (operands chosen per step): a G2 addition is ~20 000 instructions, and
-// every inlined copy would cost minutes of compile time.
+// Each kernel is written as short programs of point operations with ONE addition call site
+// (operands chosen per step): a G2 addition is ~20 000 instructions, and every inlined copy would
+// cost minutes of compile time.
 
 template <class C>
 __device__ __forceinline__ typename C::P dbl_times(typename C::P v, int k) {
@@ -232,170 +225,180 @@ __device__ __forceinline__ typename C::P dbl_times(typename C::P v, int k) {
   return v;
 }
 
-// Block epilogue shared by both levels (lds: blockDim points, 2 * blockDim with split).  v = this thread's value:
+// Block epilogue of k_rowcol_final (lds: blockDim points).  v = this thread's plain sum, base
+// its weighted sum:
 //   suffix scan over the block; V = sum_{j > i} v_j (exclusive suffix);
-//   x = base + 2^lg1 * V;
-//   compose (lg2 >= 0): x = extra + 2^lg2 * x, then the block sum of x;
-//   split   (lg2 <  0): the block sums of x and of extra side by side (two interleaved trees).
-// Thread 0 ends with lds[0] = sum x, lds[BT] = sum extra (split), *s_blk = sum v.
+//   x = base + 2^lg1 * V, then the block sum of x (a tree).
+// Thread 0 ends with lds[0] = sum x and *s_blk = sum v.
 template <class C>
 __device__ __forceinline__ void block_epilogue(typename C::P v, const typename C::P& base, int lg1,
-                                               const typename C::P& extra, int lg2, bool split, typename C::P* lds,
-                                               typename C::P* s_blk) {
+                                               typename C::P* lds, typename C::P* s_blk) {
   const uint32_t i = threadIdx.x, BT = blockDim.x;
   int lgBT = 0;
   while ((1u << lgBT) < BT) lgBT++;
-  const int n_final = lg2 >= 0 ? 2 : 1;
   store_point<C>(&lds[i], v);
   __syncthreads();
-  const int steps = 2 * lgBT + n_final;
+  const int steps = 2 * lgBT + 1;
   for (int st = 0; st < steps; st++) {
     typename C::P a = v, b;
     bool act;
-    uint32_t dst = i;
     if (st < lgBT) {  // suffix scan: v += v[i + 2^st]
       const uint32_t d = 1u << st;
       act = i + d < BT;
       if (act) b = load_point<C>(&lds[i + d]);
-    } else if (st < lgBT + n_final) {  // x = base + 2^lg1 V, then x = extra + 2^lg2 x
-      const bool first = st == lgBT;
-      if (first) {
-        b = i + 1 < BT ? load_point<C>(&lds[i + 1]) : C::identity();
-        if (i == 0) *s_blk = load_point<C>(&lds[0]);
-      } else {
-        b = v;
-      }
-      b = dbl_times<C>(b, first ? lg1 : lg2);
-      a = first ? base : extra;
+    } else if (st == lgBT) {  // x = base + 2^lg1 V
+      b = i + 1 < BT ? load_point<C>(&lds[i + 1]) : C::identity();
+      if (i == 0) *s_blk = load_point<C>(&lds[0]);
+      b = dbl_times<C>(b, lg1);
+      a = base;
       act = true;
-    } else {  // tree level with half size h: x-part on threads [0, h), extra-part on [h, 2h)
-      const uint32_t h = BT >> (st - lgBT - n_final + 1);
-      act = split ? i < 2 * h : i < h;
+    } else {  // tree level with half size h
+      const uint32_t h = BT >> (st - lgBT);
+      act = i < h;
       if (act) {
-        dst = i < h ? i : BT + (i - h);
-        a = load_point<C>(&lds[dst]);
-        b = load_point<C>(&lds[dst + h]);
+        a = load_point<C>(&lds[i]);
+        b = load_point<C>(&lds[i + h]);
       }
     }
     __syncthreads();
     if (act) {
       v = C::add(a, b);
-      store_point<C>(&lds[dst], v);
+      store_point<C>(&lds[i], v);
     }
-    if (split && st == lgBT + n_final - 1) store_point<C>(&lds[BT + i], extra);
     __syncthreads();
   }
 }
 
-// Level 1: grid = Wb * nblk blocks of BT threads (T = NB / L = nblk * BT); block
-// (w, blk) writes Y[w*nblk + blk] and S[w*nblk + blk].  A bucket spanning accumulation
-// segments s_first .. s_last has continuation partials conts[s_first+1 .. s_last]; with fold
-// they are all added here (short spans), else k_cont_seq / k_cont_treeF has already folded
-// them into conts[s_first+1].
+// ---- Row/column bucket reduction (geometry and identity in msm_rowcol.h), of one shared bucket
+// window or a bucket shard's range of it (Wb == 1: the window-table multiexps) and of the Wb
+// windows of a plain multiexp alike.  The buckets of a window, as R rows of Cn columns, are summed
+// along both axes by levels of k_rowcol_sum -- plain sums, one accumulator and one operand per
+// thread, no LDS, no barrier, every bucket added twice -- and k_rowcol_final takes the two
+// weighted sums of the Cn + R results.  Several windows lie back to back in every array (R and
+// every level's Q are powers of two then, so no group of rows straddles two windows).
+
+// Continuation fold, one thread per accumulation segment: the thread of a bucket's first
+// continuation partial (s == s_first + 1) adds the bucket's partials into bucket_sums[b] -- all of
+// conts[s_first+1 .. s_last] when the longest span is at most fold_span (`fold`; device-decided
+// from k_max_span's words when span_words is given), else conts[s_first+1], into which k_cont_seq /
+// k_cont_long / k_cont_treeF have folded them.  Almost always one addition per thread.
+// cont_bucket[s] is the accumulation's: written for every segment that begins inside the range's
+// entries [offsets[b_lo], offsets[b_hi]) (a segment the range's start cuts begins a bucket).
 template <class C>
-__global__ void __launch_bounds__(256) k_reduce_blocks(const uint32_t* counts, const uint32_t* offsets,
-                                                       const typename C::P* bucket_sums, const typename C::P* conts,
-                                                       uint32_t S, uint32_t b0, uint32_t NB, uint32_t L, int lgL,
-                                                       uint32_t nblk, int fold, typename C::P* Y, typename C::P* Ssum,
-                                                       const uint32_t* span_words, uint32_t span_g, uint32_t fold_span) {
-  extern __shared__ uint4 lds_raw[];
-  typename C::P* lds = reinterpret_cast<typename C::P*>(lds_raw);
+__global__ void __launch_bounds__(256) k_cont_fold(const uint32_t* cont_bucket, const uint32_t* counts,
+                                                   const uint32_t* offsets, uint32_t S, uint32_t b_lo, uint32_t b_hi,
+                                                   int fold, const typename C::P* conts, typename C::P* bucket_sums,
+                                                   const uint32_t* span_words, uint32_t span_g, uint32_t fold_span) {
+  // A small grid (CONT_FOLD_BLOCKS workgroups at most) strides over the workgroup-sized runs of
+  // segments that begin inside the range's entries, and only over those.  One workgroup per run
+  // of the whole multiexp's positions, as the accumulation launches, starves here: a bucket
+  // shard's range holds 1/N of the positions, and every workgroup, empty or not, has to be placed
+  // beside the accumulations first (G2: one wave per SIMD) -- a rank of 8 spent 3.4-3.8 ms in
+  // this kernel for G2 that way.
+  const uint32_t E_lo = offsets[b_lo], E_hi = offsets[b_hi];
+  const size_t per = (size_t)blockDim.x * S;
+  const size_t run_first = E_lo / per, run_end = (E_hi + per - 1) / per;
+  if (E_hi <= E_lo || run_first + blockIdx.x >= run_end) return;  // block-uniform
   if (span_words) fold = block_span(span_words, span_g) <= fold_span ? 1 : 0;  // device-decided
-  const uint32_t i = threadIdx.x;
-  const uint32_t w = blockIdx.x / nblk, blk = blockIdx.x % nblk;
-  const uint32_t gb0 = b0 + w * NB + (blk * blockDim.x + i) * L;
-  // G2 (448-byte points, one wave per SIMD): the running total `acc` waits in this thread's LDS
-  // slot (free until the epilogue) instead of registers, which the compiler otherwise spills
-  // to scratch (KB per lane)
-  constexpr bool acc_lds = sizeof(typename C::P) > 256;
-  typename C::P run = C::identity(), acc = C::identity(), bk = C::identity();
-  if (acc_lds) store_point<C>(&lds[i], acc);
-  // per bucket k = L-1 .. 0:  bk = partial (+ each continuation partial);  run += bk;  acc += run
-  int k = (int)L - 1;
-  uint32_t op = 0, c_next = 0, c_end = 0;  // op 0: load, 1: continuation, 2: run, 3: acc
-  while (k >= 0) {
-    typename C::P a, b;
-    if (op == 0) {
-      const uint32_t gb = gb0 + (uint32_t)k, cnt = counts[gb];
-      bk = C::identity();
-      c_next = c_end = 0;
-      if (cnt) {
-        bk = load_point<C>(&bucket_sums[gb]);
-        const uint32_t off = offsets[gb];
-        const uint32_t s_first = off / S, s_last = (off + cnt - 1) / S;
-        c_next = s_first + 1;
-        c_end = s_last > s_first ? (fold ? s_last + 1 : s_first + 2) : c_next;
-      }
-      op = c_next < c_end ? 1 : 2;
-      continue;
-    }
-    if (op == 1) { a = bk; b = load_point<C>(&conts[c_next]); }
-    else if (op == 2) { a = run; b = bk; }
-    else { a = acc_lds ? load_point<C>(&lds[i]) : acc; b = run; }
-    const typename C::P r = C::add(a, b);
-    if (op == 1) {
-      bk = r;
-      if (++c_next == c_end) op = 2;
-    } else if (op == 2) {
-      run = r;
-      op = 3;
-    } else {
-      if (acc_lds) store_point<C>(&lds[i], r);
-      else acc = r;
-      op = 0;
-      k--;
-    }
-  }
-  if (acc_lds) acc = load_point<C>(&lds[i]);
-  __syncthreads();  // every thread has its acc back before the epilogue reuses the slots
-  typename C::P s_blk;
-  block_epilogue<C>(run, acc, lgL, acc, -1, false, lds, &s_blk);
-  if (i == 0) {
-    store_point<C>(&Y[blockIdx.x], load_point<C>(&lds[0]));
-    store_point<C>(&Ssum[blockIdx.x], s_blk);
+  for (size_t run = run_first + blockIdx.x; run < run_end; run += gridDim.x) {
+    const uint32_t s = (uint32_t)(run * blockDim.x + threadIdx.x);
+    const size_t pos0 = (size_t)s * S;
+    if (pos0 < E_lo || pos0 >= E_hi) continue;
+    const uint32_t b = cont_bucket[s];
+    if (b == 0xffffffffu) continue;
+    const uint32_t off = offsets[b];
+    const uint32_t s_first = off / S;
+    if (s != s_first + 1) continue;
+    const uint32_t n = fold ? (off + counts[b] - 1) / S - s_first : 1u;
+    typename C::P v = load_point<C>(&bucket_sums[b]);
+    for (uint32_t i = 0; i < n; i++) v = C::add(v, load_point<C>(&conts[s + i]));
+    store_point<C>(&bucket_sums[b], v);
   }
 }
+constexpr unsigned CONT_FOLD_BLOCKS = 512;
 
-// Level 2: one block of BT2 threads per window over its nblk = BT2 * Lb (Y, S) pairs:
-//   sum_blk Y + M * sum_blk blk * S,  M = 2^lgM = L * BT (level 1's block size)
-// thread j owns blocks [j*Lb, j*Lb + Lb): P_j = sum Y, A'_j = sum_k k S, R'_j = sum_k S, and
-//   sum_blk blk S = sum_j (A'_j + Lb * V'_j),  V'_j = sum_{j' > j} R'_j'
-// -> out[w] = the window total (canonical coordinates); split (one window): out[0] = sum P,
-// out[1] = sum_blk blk * S, out[2] = sum_blk S, and the host adds 2^lgM * out[1]
-// (reduce_split_shift; out[2] is the plain bucket sum a bucket range's offset multiplies).
+// One level of plain sums: in is a rows_in x inner matrix of points, out[g][j] = the sum of rows
+// g*Q .. g*Q + Q - 1 (those below rows_in) of column j; thread g*inner + j, so a column level's
+// loads are coalesced across j and a row level (inner == 1) reads Q consecutive points per lane.
+// counts (the first level, in = the range's bucket_sums): a bucket with no entry was never
+// written and reads as the identity.  Two jobs per launch (the column and the row level of the
+// same depth): blocks [0, a.blocks) take a, the rest b.
 template <class C>
-__global__ void __launch_bounds__(256) k_reduce_window(const typename C::P* Y, const typename C::P* Ssum,
-                                                       uint32_t nblk, uint32_t Lb, int lgLb, int lgM, int split,
-                                                       typename C::P* out) {
+struct SumJob {
+  const typename C::P* in = nullptr;
+  typename C::P* out = nullptr;
+  const uint32_t* counts = nullptr;
+  uint32_t rows_in = 0, inner = 1, Q = 1, n_out = 0, blocks = 0;
+};
+template <class C>
+__global__ void __launch_bounds__(256) k_rowcol_sum(SumJob<C> a, SumJob<C> b) {
+  const bool second = blockIdx.x >= a.blocks;
+  const SumJob<C> J = second ? b : a;
+  const uint32_t i = (blockIdx.x - (second ? a.blocks : 0u)) * blockDim.x + threadIdx.x;
+  if (i >= J.n_out) return;
+  const uint32_t g = i / J.inner, j = i - g * J.inner;
+  const uint32_t r_end = min(g * J.Q + J.Q, J.rows_in);
+  typename C::P acc = C::identity();
+  for (uint32_t r = g * J.Q; r < r_end; r++) {
+    const size_t e = (size_t)r * J.inner + j;
+    if (J.counts && J.counts[e] == 0) continue;
+    acc = C::add(acc, load_point<C>(&J.in[e]));  // (the first summand: add returns it as it is)
+  }
+  store_point<C>(&J.out[i], acc);
+}
+
+// Final stage: the weighted sums of a window's Cn column sums (pass 1, weights j+1) and R row sums
+// (pass 0, weights k) by workgroups of BT threads, Lb sums each (BT * Lb >= max(Cn, R); sums past
+// the end read as identities): per-thread running sums, then the block epilogue's suffix scan
+// and tree -- 2 Lb + 2 log2 BT + 1 serial additions for under 1 % of the work.
+//   per sum k = Lb-1 .. 0 -- columns: run += Z_k; acc += run -- rows: acc += run; run += Z_k
+// lc < 0 (one shared window, two workgroups side by side): block 0 writes out[0] =
+//   sum_j (j+1) Col_j, block 1 out[1] = sum_k k Row_k and out[2] = sum_k Row_k; the host adds
+//   2^lc * out[1] (and a shard's bk_lo * out[2]).
+// lc >= 0 (one workgroup per window w, both passes in turn): 2^lc times the rows' result is
+//   thread 0's initial acc of the column pass, so out[w] = the window total.
+template <class C>
+__global__ void __launch_bounds__(256) k_rowcol_final(const typename C::P* col, uint32_t Cn, const typename C::P* row,
+                                                      uint32_t R, uint32_t Lb, int lgLb, int lc, typename C::P* out) {
   extern __shared__ uint4 lds_raw[];
   typename C::P* lds = reinterpret_cast<typename C::P*>(lds_raw);
-  const uint32_t i = threadIdx.x, w = blockIdx.x;
-  const size_t base = (size_t)w * nblk + (size_t)i * Lb;
-  typename C::P run = C::identity(), acc = C::identity(), p = C::identity();
-  // per block k = Lb-1 .. 0:  acc += run;  run += S_k;  p += Y_k  (blocks past nblk: identities,
-  // reduce_level2)
-  for (uint32_t it = 0; it < 3 * Lb; it++) {
-    const uint32_t k = Lb - 1 - it / 3, op = it % 3;
-    const bool in = i * Lb + k < nblk;
-    typename C::P a, b;
-    if (op == 0) { a = acc; b = run; }
-    else if (op == 1) { a = run; b = in ? load_point<C>(&Ssum[base + k]) : C::identity(); }
-    else { a = p; b = in ? load_point<C>(&Y[base + k]) : C::identity(); }
-    const typename C::P r = C::add(a, b);
-    if (op == 0) acc = r;
-    else if (op == 1) run = r;
-    else p = r;
-  }
-  typename C::P s_all;
-  block_epilogue<C>(run, acc, lgLb, p, split ? -1 : lgM, split != 0, lds, &s_all);
-  if (i == 0) {
-    if (split) {
-      out[0] = C::reduce(load_point<C>(&lds[blockDim.x]));
-      out[1] = C::reduce(load_point<C>(&lds[0]));
-      out[2] = C::reduce(s_all);
-    } else {
-      out[w] = C::reduce(load_point<C>(&lds[0]));
+  const uint32_t i = threadIdx.x;
+  const bool split = lc < 0;
+  const uint32_t w = split ? 0u : blockIdx.x;
+  const int p_first = split ? (blockIdx.x == 1 ? 0 : 1) : 0, p_last = split ? p_first : 1;
+#pragma unroll 1
+  for (int pass = p_first; pass <= p_last; pass++) {
+    const bool rows = pass == 0;
+    const typename C::P* in = rows ? row + (size_t)w * R : col + (size_t)w * Cn;
+    const uint32_t n = rows ? R : Cn;
+    // (the rows' result waits in out[w], not in registers: this thread wrote it)
+    typename C::P run = C::identity(), acc = C::identity();
+    if (!split && !rows && i == 0) acc = load_point<C>(&out[w]);
+    for (uint32_t it = 0; it < 2 * Lb; it++) {
+      const uint32_t k = Lb - 1 - it / 2;
+      const bool to_run = ((it & 1u) != 0) == rows;
+      typename C::P a, b;
+      if (to_run) { a = run; b = i * Lb + k < n ? load_point<C>(&in[i * Lb + k]) : C::identity(); }
+      else { a = acc; b = run; }
+      const typename C::P r = C::add(a, b);
+      if (to_run) run = r;
+      else acc = r;
     }
+    typename C::P s_all;
+    block_epilogue<C>(run, acc, lgLb, lds, &s_all);
+    if (i == 0) {
+      const typename C::P x = load_point<C>(&lds[0]);
+      if (!split) {
+        if (rows) store_point<C>(&out[w], dbl_times<C>(x, lc));
+        else out[w] = C::reduce(x);
+      } else if (rows) {
+        out[1] = C::reduce(x);
+        out[2] = C::reduce(s_all);
+      } else {
+        out[0] = C::reduce(x);
+      }
+    }
+    __syncthreads();  // (lds[0] is read before the next pass refills the slots)
   }
 }
 
@@ -791,7 +794,7 @@ size_t MsmWorkspace<C>::bytes_needed(size_t n) {
   size_t E = n * (size_t)sh.W;
   size_t nbt = (size_t)sh.Wb * sh.NB;
   size_t segs = (E + sh.S - 1) / sh.S + 1;
-  size_t T = (size_t)sh.Wb * (sh.NB / sh.L);
+  size_t T = reduce_partial_points(sh, sizeof(typename C::P) > 256);
   return E * 4 + nbt * 4 * 3 + 16 + nbt * sizeof(typename C::P) + segs * sizeof(typename C::P) +
          2 * T * sizeof(typename C::P) + n * 4;
 }
@@ -853,7 +856,7 @@ hipError_t MsmWorkspace<C>::reserve_shape(size_t n, const MsmShape& sh) {
   const size_t E = n * (size_t)sh.W;
   const size_t nbt = (size_t)sh.Wb * sh.NB;
   const size_t segs = (E + sh.S - 1) / sh.S + 1;
-  const size_t T = (size_t)sh.Wb * (sh.NB / sh.L);
+  const size_t T = reduce_partial_points(sh, sizeof(typename C::P) > 256);
   const size_t tc = sort_tilecount_words(sh, n);
   if (tc > cap_tc) {
     if (tilecounts) hipFree(tilecounts);
@@ -963,8 +966,9 @@ hipError_t msm_front(MsmWorkspace<C>& ws, hipStream_t st, const uint32_t* d_base
   return msm_accumulate<C>(ws, st, d_bases, n, sh, timing);
 }
 
-// Reduction of the buckets [b0, b0 + nbr) of each of Wb windows (window stride NB): continuation
-// fix-up, then the two-level summation by parts into out[] (Wb totals, or 3 points when split).
+// Reduction of the buckets [b0, b0 + nbr) (one shared window, or a bucket shard's range of it) or
+// of all Wb windows of NB buckets (b0 = 0, nbr = NB): continuation fix-up, then the row and column
+// sums into out[] (Wb totals, or 3 points for one shared window).
 struct SpanSrc {  // device-decided tails: k_max_span's words (null: the host decided)
   const uint32_t* words = nullptr;
   uint32_t g = 0, fold_span = 0, seq_max = 0;
@@ -985,7 +989,7 @@ AccView acc_view(const MsmWorkspace<C>& ws, size_t n, const MsmShape& sh) {
 
 template <class C>
 static void reduce_range(MsmWorkspace<C>& ws, const AccView& v, hipStream_t st, const MsmShape& sh, size_t segs,
-                         size_t span, bool fold, bool seq, uint32_t b0, uint32_t nbr, uint32_t L, uint32_t y_off,
+                         size_t span, bool fold, bool seq, uint32_t b0, uint32_t nbr,
                          typename C::P* out, const SpanSrc& dev = SpanSrc()) {
   constexpr bool G2 = sizeof(typename C::P) > 256;
   const size_t nb_all = (size_t)sh.Wb * nbr;
@@ -1009,29 +1013,48 @@ static void reduce_range(MsmWorkspace<C>& ws, const AccView& v, hipStream_t st, 
                          v.counts, v.offsets, (uint32_t)nbt, v.S, (uint32_t)stride, b0, (uint32_t)(b0 + nb_all),
                          ws.conts);
   }
-  // two-level summation by parts (k_reduce_blocks, k_reduce_window): Y/S per level-1 block
-  // in seg_weighted / seg_sum (from y_off), the totals in out
-  const uint32_t T = nbr / L;
-  const uint32_t BT = reduce_threads_for(nbr, L, G2);
-  const uint32_t nblk = T / BT;
-  uint32_t BT2, Lb;
-  reduce_level2(nblk, G2, &BT2, &Lb);
-  const int split = sh.Wb == 1 ? 1 : 0;
-  hipLaunchKernelGGL(k_reduce_blocks<C>, dim3((unsigned)(sh.Wb * nblk)), dim3(BT), BT * sizeof(typename C::P), st,
-                     v.counts, v.offsets, ws.bucket_sums, ws.conts, v.S, b0, (uint32_t)sh.NB, L, reduce_lg2(L), nblk,
-                     fold ? 1 : 0, ws.seg_weighted + y_off, ws.seg_sum + y_off, dev.words, dev.g, dev.fold_span);
-  hipLaunchKernelGGL(k_reduce_window<C>, dim3((unsigned)sh.Wb), dim3(BT2), 2 * BT2 * sizeof(typename C::P), st,
-                     ws.seg_weighted + y_off, ws.seg_sum + y_off, nblk, Lb, reduce_lg2(Lb),
-                     reduce_lg2(L) + reduce_lg2(BT), split, out);
+  // continuation fold, then the row and column sums (msm_rowcol.h) of every window: column
+  // partials in seg_weighted, row partials in seg_sum (each level's output Wb windows back to
+  // back), the totals by k_rowcol_final
+  const uint32_t Wb = (uint32_t)sh.Wb;
+  const unsigned fold_blocks = std::max(1u, std::min(msm_blocks_for(segs, 256), CONT_FOLD_BLOCKS));
+  hipLaunchKernelGGL(k_cont_fold<C>, dim3(fold_blocks), dim3(256), 0, st, ws.cont_bucket, v.counts, v.offsets, v.S,
+                     b0, (uint32_t)(b0 + nb_all), fold ? 1 : 0, ws.conts, ws.bucket_sums, dev.words, dev.g,
+                     dev.fold_span);
+  const RowColGeom g = rowcol_geom(nbr, ROWCOL_QLG, G2);
+  const uint32_t B = G2 ? 128 : 256;
+  for (int lv = 0; lv < std::max(g.ncol, g.nrow); lv++) {
+    SumJob<C> job[2];
+    for (int r = 0; r < 2; r++) {
+      if (lv >= (r ? g.nrow : g.ncol)) continue;
+      const RowColLevel* ls = r ? g.row : g.col;
+      typename C::P* part = r ? ws.seg_sum : ws.seg_weighted;
+      SumJob<C>& j = job[r];
+      j.in = lv ? part + (size_t)Wb * ls[lv - 1].out_off : ws.bucket_sums + b0;
+      j.out = part + (size_t)Wb * ls[lv].out_off;
+      j.counts = lv ? nullptr : v.counts + b0;
+      j.rows_in = Wb * ls[lv].rows_in;
+      j.inner = ls[lv].inner;
+      j.Q = ls[lv].Q;
+      j.n_out = Wb * ls[lv].rows_out * ls[lv].inner;
+      j.blocks = msm_blocks_for(j.n_out, B);
+    }
+    hipLaunchKernelGGL(k_rowcol_sum<C>, dim3(job[0].blocks + job[1].blocks), dim3(B), 0, st, job[0], job[1]);
+  }
+  hipLaunchKernelGGL(k_rowcol_final<C>, dim3(Wb == 1 ? 2u : Wb), dim3(g.final_threads),
+                     g.final_threads * sizeof(typename C::P), st,
+                     ws.seg_weighted + (size_t)Wb * g.col[g.ncol - 1].out_off, g.Cn,
+                     ws.seg_sum + (size_t)Wb * g.row[g.nrow - 1].out_off, g.R, g.final_per_thread,
+                     reduce_lg2(g.final_per_thread), Wb == 1 ? -1 : g.lc, out);
 }
 
-// Back half: continuation fix-up, summation by parts and the per-window sums, copied to host_out
+// Back half: continuation fix-up, row and column sums and the per-window sums, copied to host_out
 // (Wb entries; 2 for one shared window, 3 for a bucket shard).
 template <class C>
 hipError_t msm_back(MsmWorkspace<C>& ws, hipStream_t st, size_t n, const MsmShape& sh, typename C::P* host_out,
                     int max_span, hipEvent_t acc_done, const uint32_t* d_span_words) {
   // continuation partials: a bucket spanning up to REDUCE_FOLD_SPAN segments has them added
-  // by its reduction thread (no extra launch); longer spans (known from the sort) are folded
+  // one after another by k_cont_fold's thread; longer spans (known from the sort) are folded
   // first -- Q threads per bucket, or log-depth 4-ary tree levels
   constexpr size_t REDUCE_FOLD_SPAN = 8;
   const AccView v = acc_view<C>(ws, n, sh);
@@ -1047,7 +1070,7 @@ hipError_t msm_back(MsmWorkspace<C>& ws, hipStream_t st, size_t n, const MsmShap
     dev.seq_max = (uint32_t)cont_seq_max();
   }
   (void)acc_done;  // (stream order: the caller's st already follows the accumulation)
-  reduce_range<C>(ws, v, st, sh, segs, span, fold, seq, sh.red_lo(), sh.red_nb(), (uint32_t)sh.L, 0, ws.window_sums,
+  reduce_range<C>(ws, v, st, sh, segs, span, fold, seq, sh.red_lo(), sh.red_nb(), ws.window_sums,
                   dev);
   const int outs = sh.bucket_shard() ? 3 : (sh.Wb == 1 ? 2 : sh.Wb);
   hipMemcpyAsync(host_out, ws.window_sums, outs * sizeof(typename C::P), hipMemcpyDeviceToHost, st);
@@ -1066,12 +1089,12 @@ void msm_back_kernels(std::vector<KernInfo>& v) {
   constexpr bool G2 = sizeof(typename C::P) > 256;
   const size_t P = sizeof(typename C::P);
   const int B = G2 ? 128 : 256, BT = (int)reduce_block_max(G2);
-  v.push_back({G2 ? "k_reduce_blocks<G2>" : "k_reduce_blocks<G1>", (const void*)k_reduce_blocks<C>, BT, BT * P});
-  v.push_back({G2 ? "k_reduce_window<G2>" : "k_reduce_window<G1>", (const void*)k_reduce_window<C>, BT,
-               2 * BT * P});
   v.push_back({G2 ? "k_cont_seq<G2>" : "k_cont_seq<G1>", (const void*)k_cont_seq<C, 4>, B, B * P});
   v.push_back({G2 ? "k_cont_long<G2>" : "k_cont_long<G1>", (const void*)k_cont_long<C>, B, B * P});
   v.push_back({G2 ? "k_cont_treeF<G2>" : "k_cont_treeF<G1>", (const void*)k_cont_treeF<C, 4>, 256, 0});
+  v.push_back({G2 ? "k_cont_fold<G2>" : "k_cont_fold<G1>", (const void*)k_cont_fold<C>, 256, 0});
+  v.push_back({G2 ? "k_rowcol_sum<G2>" : "k_rowcol_sum<G1>", (const void*)k_rowcol_sum<C>, B, 0});
+  v.push_back({G2 ? "k_rowcol_final<G2>" : "k_rowcol_final<G1>", (const void*)k_rowcol_final<C>, BT, BT * P});
 }
 
 template <class C>

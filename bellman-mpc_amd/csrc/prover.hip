@@ -398,7 +398,9 @@ bool bucket_shards_use(int device, size_t na, size_t nshards, int co_ranks) {
 }
 
 // Rank `shard` of N: its bucket range [lo, hi), granule-aligned, balancing the expected
-// accumulation (used * bucket_cdf) plus the reduction (3 additions per bucket).  False when the bucket set is too small to give every rank several granules.
+// accumulation (used * bucket_cdf) plus the reduction, weighted kw = 3 mixed additions per bucket
+// (the row/column sums add every bucket twice, with full additions, and its continuation
+// partials once).  False when the bucket set is too small to give every rank several granules.
 bool bucket_shard_range(int c, size_t used, size_t shard, size_t N, uint32_t* lo, uint32_t* hi) {
   const int W = (256 + c - 1) / c;
   const uint32_t NB = 1u << (c - 1);
@@ -763,22 +765,6 @@ bool prover_serial() {  // (read per proof: tests/test_gpu_parity.py runs both m
   return e && e[0] == '1';
 }
 
-// resident threads of the G1 bucket reduction (k_reduce_blocks) on every CU (full) or on the
-// CU-masked tail streams' quarter of them
-size_t reduce_resident_threads(bh_ctx* ctx, bool full) {
-  // occupancy is a property of the kernel (one code object for every device); the CU count is
-  // the context's device's, read once per device (contexts on several devices, concurrently)
-  static const size_t per_cu = reduce_blocks_resident_per_cu_g1();
-  static std::once_flag once[64];
-  static int ncu[64];
-  const int d = ctx->device & 63;
-  std::call_once(once[d], [&] {
-    if (hipDeviceGetAttribute(&ncu[d], hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) ncu[d] = 1;
-  });
-  const int cus = full ? ncu[d] : std::max(1, ncu[d] / 4);
-  return per_cu * (size_t)std::max(cus, 1);
-}
-
 // When an exchanger is given (RCCL ranks, or the one-device emulation's virtual ranks) and
 // the rank count qualifies, the H block is distributed (dist_h.h): this rank's h multiexp then
 // covers the share of h it ends with instead of the range [shard*(m-1)/N, ...).
@@ -981,13 +967,6 @@ bh_status compute_msms(bh_ctx* ctx, const bh_params* params, const bh_witness* w
       MsmShape& sh = shapes[j];
       sh.bk_lo = jobs[j].bk_lo;
       sh.bk_hi = jobs[j].bk_hi;
-      // reduction geometry: L * BT divides the granule (BUCKET_SHARD_GRANULE), and at least as many
-      // reduction threads as one GPU's whole bucket set gets (msm_shape_table: 16 384), since a
-      // shard's buckets hold as many continuation partials each (a round-5 rank of 8: G2 with 8 192
-      // threads was a 4.6 ms reduction at the end of the proof)
-      const uint32_t BT = reduce_block_max(jobs[j].g2);
-      while (sh.L > 1 && ((uint32_t)sh.L * BT > BUCKET_SHARD_GRANULE || sh.red_nb() / (uint32_t)sh.L < 16384u))
-        sh.L >>= 1;
       // segments sized for the range's expected entries (the grid still covers every position)
       const double f = bucket_cdf(sh.c, sh.W, sh.bk_hi) - bucket_cdf(sh.c, sh.W, sh.bk_lo);
       const size_t E = std::max<size_t>((size_t)((double)jobs[j].used * f), 1);
@@ -1191,23 +1170,9 @@ bh_status compute_msms(bh_ctx* ctx, const bh_params* params, const bh_witness* w
   int h_pos = nbig;
   for (int q = 0; q < nbig; q++)
     if (jobs[big[q]].is_h) h_pos = q;
-  // The last accumulated multiexp's reduction tail runs alone on an idle GPU, at the end of
-  // the critical path: give its bucket reduction more, shorter chains (fewer buckets per
-  // thread: 2L + 2 log2(BT) + log2(L) serial point operations in k_reduce_blocks), while
-  // the earlier tails, which share the SIMDs with accumulations, keep the work-lean shape.
   // (Tried and removed: the last multiexp accumulated and reduced as two bucket halves so the
   // lower half's reduction runs beside the upper half's accumulation, +0.8 ms per 2^22 proof,
   // profiles/r03_ab_last_halves.txt; fewer rounds for the last accumulation, within noise.)
-  if (nbig > 0) {
-    MsmShape& sl = shapes[big[nbig - 1]];
-    // one round of resident k_reduce_blocks blocks on the CUs the last tail runs on
-    const int last_threads =
-        last_full ? (int)std::min<size_t>(reduce_resident_threads(ctx, true), 1 << 20) : 65536;
-    const int nb = (int)sl.red_nb();
-    int L = sl.L;
-    while (L > 1 && (size_t)sl.Wb * (size_t)(nb / L) < (size_t)last_threads) L >>= 1;
-    sl.L = L;
-  }
   // H placement.  A resident witness enqueues H first, running beside everything: since the G2
   // accumulation keeps ZZ/ZZZ in LDS (268 registers, msm_impl.cuh accumulate_lds) H's NTT passes
   // co-reside with it (same-box A/B at 2^22: 55.1-55.3 ms per proof against 57.4-58.2 with H after

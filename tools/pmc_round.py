@@ -23,7 +23,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from pmc_report import load  # noqa: E402
 
 KERNELS = ["k_accumulate_pf<CurveOps<FpOps", "k_accumulate_pf<CurveOps<Fp2Ops", "k_ntt_pass<true>",
-           "k_ntt_pass<false>", "k_reduce_blocks", "k_reduce_window", "k_part_", "k_cont_seq", "k_dist"]
+           "k_ntt_pass<false>", "k_rowcol_sum", "k_rowcol_final", "k_cont_fold", "k_part_", "k_cont_seq",
+           "k_dist"]
 G1 = KERNELS[0]
 
 
