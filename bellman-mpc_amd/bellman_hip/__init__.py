@@ -167,7 +167,27 @@ def _load():
         "bh_r1cs_eval": (I, [P, P, P, P, P, P]),
         "bh_generate_parameters": (I, [P, P, P, P, P, P, P, P]),
         "bh_chain_r1cs": (I, [P, S, U64, P]),
+        "bh_srs_mul_each": (I, [P, P, P, S, P]),
+        "bh_srs_mul_each_bounded": (I, [P, P, P, S, I, P]),
+        "bh_srs_mul_powers": (I, [P, P, P, P, I, P]),
+        "bh_srs_sub_range": (I, [P, P, S, S, S, P]),
+        "bh_mpc_common_initial": (I, [P, S, P]),
+        "bh_mpc_common_contribute": (I, [P, P, P, P, P, P]),
+        "bh_mpc_common_verify": (I, [P, P, P, P, P, P]),
+        "bh_mpc_common_h_basis": (I, [P, P, S, P, P]),
+        "bh_mpc_common_len": (S, [P]),
+        "bh_mpc_uncommon_initial": (I, [P, P, P, P, P, P, P, P]),
+        "bh_mpc_uncommon_contribute": (I, [P, P, P, P, P]),
+        "bh_mpc_uncommon_verify": (I, [P, P, P, P, P, S, P, P]),
+        "bh_mpc_last_miller_ms": (ctypes.c_double, []),
     }
+    for kind in ("common", "uncommon"):
+        for who in ("", "_contrib"):
+            sig[f"bh_mpc_{kind}{who}_free"] = (I, [P])
+            sig[f"bh_mpc_{kind}{who}_vector"] = (I, [P, I, P] if not who else [P, I, I, P])
+            sig[f"bh_mpc_{kind}{who}_point"] = (I, [P, I, P])
+            sig[f"bh_mpc_{kind}{who}_write"] = (I, [P, P, S, P])
+            sig[f"bh_mpc_{kind}{who}_read"] = (I, [P, P, S, I, P])
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
         f.restype = res
@@ -197,8 +217,12 @@ EXPORTED_SYMBOLS = [
     "bh_evdom_icoset_fft", "bh_evdom_distribute_powers", "bh_evdom_divide_by_z_on_coset", "bh_evdom_mul_assign",
     "bh_evdom_sub_assign", "bh_evdom_read", "bh_evdom_write", "bh_evdom_into_scalars", "bh_evdom_sync",
     "bh_evdom_free", "bh_r1cs_create", "bh_r1cs_free", "bh_r1cs_sizes", "bh_r1cs_eval", "bh_generate_parameters",
-    "bh_chain_r1cs",
-]
+    "bh_chain_r1cs", "bh_srs_mul_each", "bh_srs_mul_each_bounded", "bh_srs_mul_powers", "bh_srs_sub_range",
+    "bh_mpc_common_initial", "bh_mpc_common_contribute", "bh_mpc_common_verify", "bh_mpc_common_h_basis",
+    "bh_mpc_common_len", "bh_mpc_uncommon_initial", "bh_mpc_uncommon_contribute", "bh_mpc_uncommon_verify",
+    "bh_mpc_last_miller_ms",
+] + [f"bh_mpc_{kind}{who}_{op}" for kind in ("common", "uncommon") for who in ("", "_contrib")
+     for op in ("free", "vector", "point", "write", "read")]
 BH_VEC_H, BH_VEC_L, BH_VEC_A, BH_VEC_B_G1, BH_VEC_B_G2 = range(5)
 PARTIAL_BYTES = 960
 
@@ -366,16 +390,64 @@ class Bases:
     def __len__(self):
         return _lib.bh_srs_len(self.h)
 
+    @classmethod
+    def _adopt(cls, ctx, group, handle):
+        """A bh_srs the library returned (owned: freed with the object)."""
+        b = cls.__new__(cls)
+        b.h, b.group, b.ctx = handle, group, ctx
+        return b
+
     def get(self, i):
         out = np.zeros(96 if self.group == BH_G1 else 192, dtype=np.uint8)
         _check(_lib.bh_srs_get(self.h, i, _ptr(out)))
         return out.tobytes()
+
+    def mul_each(self, scalars, nbits=None):
+        """out[i] = k_i * self[i] (ints below r); one scalar for a longer vector multiplies every
+        element.  nbits: an upper bound on the scalars' width (bh_srs_mul_each_bounded)."""
+        k = np.ascontiguousarray(np.stack([fr_canonical_words(x) for x in scalars]) if len(scalars)
+                                 else np.zeros((1, 4), np.uint64))
+        h = ctypes.c_void_p()
+        if nbits is None and len(scalars) == len(self):
+            _check(_lib.bh_srs_mul_each(self.ctx.h, self.h, _ptr(k), len(scalars), ctypes.byref(h)), "bh_srs_mul_each")
+        else:
+            _check(_lib.bh_srs_mul_each_bounded(self.ctx.h, self.h, _ptr(k), len(scalars),
+                                                255 if nbits is None else int(nbits), ctypes.byref(h)),
+                   "bh_srs_mul_each_bounded")
+        return Bases._adopt(self.ctx, self.group, h)
+
+    def mul_powers(self, a, x, invert=False):
+        """make_new_tau_paramter (mpc.rs:677-706): out[i] = (a * x^i)^(+-1) * self[i]."""
+        h = ctypes.c_void_p()
+        _check(_lib.bh_srs_mul_powers(self.ctx.h, self.h, _ptr(fr_canonical_words(a)), _ptr(fr_canonical_words(x)),
+                                      int(bool(invert)), ctypes.byref(h)), "bh_srs_mul_powers")
+        return Bases._adopt(self.ctx, self.group, h)
+
+    def sub_range(self, lo1, lo2, n):
+        """out[i] = self[lo2 + i] - self[lo1 + i], i < n (mpc.rs:631-635)."""
+        h = ctypes.c_void_p()
+        _check(_lib.bh_srs_sub_range(self.ctx.h, self.h, lo1, lo2, n, ctypes.byref(h)), "bh_srs_sub_range")
+        return Bases._adopt(self.ctx, self.group, h)
+
+    def to_bytes(self):
+        return b"".join(self.get(i) for i in range(len(self)))
 
     def __del__(self):
         try:
             _lib.bh_srs_free(self.h)
         except Exception:
             pass
+
+
+class BorrowedBases(Bases):
+    """A vector that belongs to another handle (a ceremony storage, a contribution), which it
+    keeps referenced; never freed on its own."""
+
+    def __init__(self, ctx, group, handle, owner):
+        self.h, self.group, self.ctx, self.owner = handle, group, ctx, owner
+
+    def __del__(self):
+        pass
 
 
 class FullDensity:
@@ -1297,3 +1369,180 @@ class Comm:
         if self.h:
             _lib.bh_comm_destroy(self.h)
             self.h = None
+
+
+# ------------------------------------------------------------------ MPC ceremony (groth16/mpc.rs)
+(BH_MPC_TAU_G1, BH_MPC_TAU_G2, BH_MPC_ALPHA_TAU_G1, BH_MPC_ALPHA_TAU_G2, BH_MPC_BETA_TAU_G1,
+ BH_MPC_BETA_TAU_G2) = range(6)
+BH_MPC_KIN_G1, BH_MPC_KIN_G2, BH_MPC_KOUT_G1, BH_MPC_KOUT_G2, BH_MPC_H_G1, BH_MPC_H_G2 = range(6)
+
+
+class _MpcHandle:
+    """Shared plumbing of the four ceremony handles; _KIND names the C functions."""
+    _KIND = ""
+    _POINTS = ()
+    _VECTORS = ()
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    def _fn(self, op):
+        return getattr(_lib, f"bh_mpc_{self._KIND}_{op}")
+
+    def write(self):
+        n = ctypes.c_size_t()
+        _check(self._fn("write")(self.h, None, 0, ctypes.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        _check(self._fn("write")(self.h, _ptr(out), n.value, ctypes.byref(n)))
+        return out[:n.value].tobytes()
+
+    @classmethod
+    def read(cls, ctx, data: bytes, checked=True):
+        buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
+        h = ctypes.c_void_p()
+        _check(getattr(_lib, f"bh_mpc_{cls._KIND}_read")(ctx.h, _ptr(buf), len(data), int(checked), ctypes.byref(h)),
+               f"{cls.__name__}::read")
+        return cls(ctx, h)
+
+    def point(self, which):
+        """Uncompressed bytes of point `which` (names: see _POINTS)."""
+        if isinstance(which, str):
+            which = self._POINTS.index(which)
+        out = np.zeros(192 if which & 1 else 96, dtype=np.uint8)
+        _check(self._fn("point")(self.h, which, _ptr(out)))
+        return out.tobytes()
+
+    def __del__(self):
+        try:
+            self._fn("free")(self.h)
+        except Exception:
+            pass
+
+
+class _MpcStorage(_MpcHandle):
+    def vector(self, which):
+        """Vector `which` (BH_MPC_* or its name) as borrowed Bases."""
+        if isinstance(which, str):
+            which = self._VECTORS.index(which)
+        h = ctypes.c_void_p()
+        _check(self._fn("vector")(self.h, which, ctypes.byref(h)))
+        return BorrowedBases(self.ctx, BH_G2 if which & 1 else BH_G1, h, self)
+
+    def __getattr__(self, name):
+        if name in type(self)._POINTS:
+            return self.point(name)
+        if name in type(self)._VECTORS:
+            return self.vector(name)
+        raise AttributeError(name)
+
+
+class _MpcContrib(_MpcHandle):
+    def vector(self, which, mine=False):
+        """The g1/g2 results (or the player's "mine" list) of vector pair element `which`."""
+        if isinstance(which, str):
+            which = self._VECTORS.index(which)
+        h = ctypes.c_void_p()
+        _check(self._fn("vector")(self.h, which, int(bool(mine)), ctypes.byref(h)))
+        return BorrowedBases(self.ctx, BH_G2 if which & 1 else BH_G1, h, self)
+
+
+class CommonParamterInStorage(_MpcStorage):
+    """mpc.rs:398-414, device-resident."""
+    _KIND = "common"
+    _POINTS = ("alpha_g1", "alpha_g2", "beta_g1", "beta_g2")
+    _VECTORS = ("tau_g1", "tau_g2", "alpha_mul_tau_g1", "alpha_mul_tau_g2", "beta_mul_tau_g1", "beta_mul_tau_g2")
+
+    def __len__(self):
+        return _lib.bh_mpc_common_len(self.h)
+
+    def h_basis(self, n):
+        """The matrixed_h part of matrix (mpc.rs:631-635): (tau_g1[n + i] - tau_g1[i], the same in G2)."""
+        a, b = ctypes.c_void_p(), ctypes.c_void_p()
+        _check(_lib.bh_mpc_common_h_basis(self.ctx.h, self.h, n, ctypes.byref(a), ctypes.byref(b)),
+               "bh_mpc_common_h_basis")
+        return Bases._adopt(self.ctx, BH_G1, a), Bases._adopt(self.ctx, BH_G2, b)
+
+
+class CommonParamter(_MpcContrib):
+    """mpc.rs:362-373: one player's round-one contribution."""
+    _KIND = "common_contrib"
+    _POINTS = tuple(f"{p}_{f}" for p in ("alpha", "beta") for f in ("g1_result", "g2_result", "g1_mine", "g2_mine"))
+    _VECTORS = CommonParamterInStorage._VECTORS
+
+
+class UnCommonParamterInStorage(_MpcStorage):
+    """mpc.rs:926-942, device-resident."""
+    _KIND = "uncommon"
+    _POINTS = ("gamma_g1", "gamma_g2", "delta_g1", "delta_g2")
+    _VECTORS = ("kin_g1", "kin_g2", "kout_g1", "kout_g2", "h_g1", "h_g2")
+
+
+class UnCommonParamter(_MpcContrib):
+    """mpc.rs:891-902: one player's round-two contribution."""
+    _KIND = "uncommon_contrib"
+    _POINTS = tuple(f"{p}_{f}" for p in ("gamma", "delta") for f in ("g1_result", "g2_result", "g1_mine", "g2_mine"))
+    _VECTORS = UnCommonParamterInStorage._VECTORS
+
+
+def _z_words(z):
+    return np.ascontiguousarray(np.stack([fr_canonical_words(x) for x in z]) if len(z) else np.zeros((1, 4), np.uint64))
+
+
+def random_z(n, rng=None):
+    """n nonzero 128-bit scalars for the batched verifications (the reference's verifiers draw theirs
+    from a CryptoRng)."""
+    import secrets
+    return [(rng.getrandbits(128) if rng else secrets.randbits(128)) or 1 for _ in range(n)]
+
+
+def initial_common_paramters(ctx, length):
+    """mpc.rs:708-728"""
+    h = ctypes.c_void_p()
+    _check(_lib.bh_mpc_common_initial(ctx.h, length, ctypes.byref(h)), "bh_mpc_common_initial")
+    return CommonParamterInStorage(ctx, h)
+
+
+def mpc_common_paramters_generator(ctx, storage, alpha_beta_tau):
+    """mpc.rs:730-785; (alpha, beta, tau) as ints below r."""
+    w = [fr_canonical_words(x) for x in alpha_beta_tau]
+    h = ctypes.c_void_p()
+    _check(_lib.bh_mpc_common_contribute(ctx.h, storage.h, *[_ptr(x) for x in w], ctypes.byref(h)),
+           "bh_mpc_common_contribute")
+    return CommonParamter(ctx, h)
+
+
+def verify_common_paramter(ctx, storage, new_paramter, z=None):
+    """mpc.rs:806-862: the next storage, or None where the reference's assert fails.  z: len(storage)
+    nonzero scalars (default: fresh 128-bit random ones)."""
+    z = random_z(len(storage)) if z is None else z
+    valid, h = ctypes.c_int(), ctypes.c_void_p()
+    _check(_lib.bh_mpc_common_verify(ctx.h, storage.h, new_paramter.h, _ptr(_z_words(z)), ctypes.byref(valid),
+                                     ctypes.byref(h)), "bh_mpc_common_verify")
+    return CommonParamterInStorage(ctx, h) if valid.value else None
+
+
+def initial_uncommon_paramters(ctx, front_g1, front_g2, back_g1, back_g2, h_g1, h_g2):
+    """mpc.rs:993-1015 from CommonParamterMatrix's six vectors (Bases)."""
+    h = ctypes.c_void_p()
+    _check(_lib.bh_mpc_uncommon_initial(ctx.h, front_g1.h, front_g2.h, back_g1.h, back_g2.h, h_g1.h, h_g2.h,
+                                        ctypes.byref(h)), "bh_mpc_uncommon_initial")
+    return UnCommonParamterInStorage(ctx, h)
+
+
+def mpc_uncommon_paramters_generator(ctx, storage, gamma_delta):
+    """mpc.rs:1017-1063; (gamma, delta) as ints below r."""
+    w = [fr_canonical_words(x) for x in gamma_delta]
+    h = ctypes.c_void_p()
+    _check(_lib.bh_mpc_uncommon_contribute(ctx.h, storage.h, *[_ptr(x) for x in w], ctypes.byref(h)),
+           "bh_mpc_uncommon_contribute")
+    return UnCommonParamter(ctx, h)
+
+
+def verify_uncommon_paramter(ctx, matrix, storage, new_paramter, z=None):
+    """mpc.rs:1065-1131; matrix: what initial_uncommon_paramters returned."""
+    n = max(len(storage.vector(k)) for k in (0, 2, 4))
+    z = random_z(n) if z is None else z
+    valid, h = ctypes.c_int(), ctypes.c_void_p()
+    _check(_lib.bh_mpc_uncommon_verify(ctx.h, matrix.h, storage.h, new_paramter.h, _ptr(_z_words(z)), len(z),
+                                       ctypes.byref(valid), ctypes.byref(h)), "bh_mpc_uncommon_verify")
+    return UnCommonParamterInStorage(ctx, h) if valid.value else None

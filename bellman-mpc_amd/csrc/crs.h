@@ -13,6 +13,11 @@ template <class C>
 hipError_t fixed_base_batch(const uint32_t* d_table, const uint32_t* d_scalars, size_t n, void* d_xyzz,
                             void* d_scratch, uint32_t* d_out, hipStream_t st);
 
+// n XYZZ points (none the identity) -> packed affine in the bh_srs layout, one inversion per 32
+// points (k_normalize); d_scratch: n field elements
+template <class C>
+hipError_t normalize_batch(const void* d_xyzz, size_t n, void* d_scratch, uint32_t* d_out, hipStream_t st);
+
 // Window table of a fixed base vector (the prover's SRS): out[i*W + w] = 2^(c*w) * P_i,
 // packed affine like the input but in records of `rec` u32 words (a whole number of
 // 128-byte lines: one line per G1 gather, two per G2), for the n points of d_pts (none

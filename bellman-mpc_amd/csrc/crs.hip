@@ -140,6 +140,19 @@ __global__ void __launch_bounds__(64) k_normalize(const typename C::P* pts, size
 }
 
 template <class C>
+hipError_t normalize_batch(const void* d_xyzz, size_t n, void* d_scratch, uint32_t* d_out, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  using P = typename C::P;
+  constexpr int CHUNK = 32;
+  const size_t threads = (n + CHUNK - 1) / CHUNK;
+  hipLaunchKernelGGL((k_normalize<C, CHUNK>), dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, st,
+                     reinterpret_cast<const P*>(d_xyzz), n,
+                     reinterpret_cast<typename FieldOf<C>::F::T*>(d_scratch), d_out,
+                     (uint32_t)(2 * FieldOf<C>::F::PACKED_WORDS), 0);
+  return hipGetLastError();
+}
+
+template <class C>
 hipError_t fixed_base_batch(const uint32_t* d_table, const uint32_t* d_scalars, size_t n, void* d_xyzz,
                             void* d_scratch, uint32_t* d_out, hipStream_t st) {
   if (n == 0) return hipSuccess;
@@ -205,6 +218,8 @@ template hipError_t window_table<G1Ops>(const uint32_t*, size_t, int, int, uint3
 template hipError_t window_table<G2Ops>(const uint32_t*, size_t, int, int, uint32_t*, uint32_t, void*, size_t,
                                         hipStream_t);
 
+template hipError_t normalize_batch<G1Ops>(const void*, size_t, void*, uint32_t*, hipStream_t);
+template hipError_t normalize_batch<G2Ops>(const void*, size_t, void*, uint32_t*, hipStream_t);
 template hipError_t fixed_base_batch<G1Ops>(const uint32_t*, const uint32_t*, size_t, void*, void*, uint32_t*,
                                             hipStream_t);
 template hipError_t fixed_base_batch<G2Ops>(const uint32_t*, const uint32_t*, size_t, void*, void*, uint32_t*,

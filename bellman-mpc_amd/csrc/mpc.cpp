@@ -1,0 +1,749 @@
+// The two parameter rounds of the fork's multi-party trusted setup (reference groth16/mpc.rs) for
+// any length and any Fr scalar, on device-resident vectors.
+//
+//   round one, "common"    CommonParamterInStorage / CommonParamter           mpc.rs:362-414
+//     initial_common_paramters, mpc_common_paramters_generator, verify_common_paramter
+//                                                                              mpc.rs:708-862
+//     the matrixed_h part of CommonParamterInStorage::matrix                   mpc.rs:631-635
+//   round two, "uncommon"  UnCommonParamterInStorage / UnCommonParamter        mpc.rs:891-1131
+//
+// Both rounds have one shape: a storage holds two (G1, G2) point pairs and three (G1, G2) vector
+// pairs; a contribution holds a ParameterPair (g1_result, g2_result, g1_mine, g2_mine) for each
+// point pair and a TauParameterPair (a list of ParameterPairs) for each vector pair.  The player's
+// side is varbase.hip's per-element multiplication for the results and crs.hip's fixed-base path
+// for the "mine" lists; the verifier batches the reference's per-element pairing checks with the
+// caller's random z_i over verify.cpp's Miller loop.
+#include <string.h>
+
+#include <algorithm>
+#include <memory>
+
+#include "pairing.h"
+#include "r1cs.h"
+#include "varbase.h"
+
+using namespace bh;
+
+namespace {
+
+struct MpcStorage {
+  bh_ctx* ctx = nullptr;
+  // common: alpha, beta; uncommon: gamma, delta
+  AffinePt<Fp> p1[2];
+  AffinePt<Fp2> p2[2];
+  // common: tau, alpha_mul_tau, beta_mul_tau; uncommon: kin, kout, h -- (g1, g2) each
+  std::unique_ptr<bh_srs> v[6];
+};
+
+struct HostPair {  // ParameterPair, mpc.rs:16-29
+  AffinePt<Fp> r1, m1;
+  AffinePt<Fp2> r2, m2;
+};
+
+struct MpcContrib {
+  bh_ctx* ctx = nullptr;
+  HostPair pp[2];
+  std::unique_ptr<bh_srs> res[6], mine[6];
+};
+
+}  // namespace
+
+struct bh_mpc_common : MpcStorage {};
+struct bh_mpc_uncommon : MpcStorage {};
+struct bh_mpc_common_contrib : MpcContrib {};
+struct bh_mpc_uncommon_contrib : MpcContrib {};
+
+namespace {
+
+AffinePt<Fp> g1_gen() { return jac_to_affine(crs_g1_gen()); }
+AffinePt<Fp2> g2_gen() { return jac_to_affine(crs_g2_gen()); }
+template <class T>
+AffinePt<T> pt_mul(const AffinePt<T>& p, const uint64_t k[4]) {
+  return jac_to_affine(jac_mul(jac_from_affine(p), k, 4));
+}
+template <class T>
+AffinePt<T> pt_neg(AffinePt<T> p) {
+  if (!p.infinity) p.y = neg(p.y);
+  return p;
+}
+// device vector -> host affine points (caller holds ctx->mu; the stream is idle)
+bh_status download_g1(const bh_srs* s, std::vector<AffinePt<Fp>>* out) {
+  std::vector<uint32_t> w(s->n * 24);
+  if (s->n) BH_TRY_HIP(hipMemcpy(w.data(), s->pts.p, s->n * 96, hipMemcpyDeviceToHost));
+  out->resize(s->n);
+  for (size_t i = 0; i < s->n; i++)
+    (*out)[i] = AffinePt<Fp>{fp_from_dev_words_g1(&w[i * 24]), fp_from_dev_words_g1(&w[i * 24 + 12]), false};
+  for (size_t i : s->identity_idx) (*out)[i].infinity = true;
+  return BH_OK;
+}
+bh_status download_g2(const bh_srs* s, std::vector<AffinePt<Fp2>>* out) {
+  std::vector<uint32_t> w(s->n * 48);
+  if (s->n) BH_TRY_HIP(hipMemcpy(w.data(), s->pts.p, s->n * 192, hipMemcpyDeviceToHost));
+  out->resize(s->n);
+  for (size_t i = 0; i < s->n; i++) {
+    const uint32_t* p = &w[i * 48];
+    (*out)[i] = AffinePt<Fp2>{Fp2{fp_from_dev_words(p), fp_from_dev_words(p + 12)},
+                              Fp2{fp_from_dev_words(p + 24), fp_from_dev_words(p + 36)}, false};
+  }
+  for (size_t i : s->identity_idx) (*out)[i].infinity = true;
+  return BH_OK;
+}
+
+bh_status clone_srs(bh_ctx* ctx, const bh_srs* in, std::unique_ptr<bh_srs>* out) {
+  std::unique_ptr<bh_srs> r(new bh_srs());
+  r->ctx = ctx;
+  r->group = in->group;
+  r->n = in->n;
+  r->identity_idx = in->identity_idx;
+  const size_t bytes = in->n * (in->group == BH_G1 ? 96 : 192);
+  BH_TRY_HIP(r->pts.alloc(std::max<size_t>(bytes, 16)));
+  if (bytes) {
+    BH_TRY_HIP(hipMemcpyAsync(r->pts.p, in->pts.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  *out = std::move(r);
+  return BH_OK;
+}
+
+bool same_device(const bh_ctx* ctx, const bh_srs* s) { return s && s->ctx && s->ctx->device == ctx->device; }
+
+// ---------------------------------------------------------------- the player's side
+struct Tables {
+  bh_srs t1, t2;
+  bh_status upload(bh_ctx* ctx) {
+    const auto a = crs_table_g1();
+    const auto b = crs_table_g2();
+    bh_status s = srs_upload_affine(ctx, BH_G1, a.data(), a.size(), &t1);
+    if (s) return s;
+    return srs_upload_affine(ctx, BH_G2, b.data(), b.size(), &t2);
+  }
+};
+
+// make_new_paramter (mpc.rs:647-675) with inverse == false
+HostPair new_pair(const AffinePt<Fp>& o1, const AffinePt<Fp2>& o2, const uint64_t k[4]) {
+  return HostPair{pt_mul(o1, k), pt_mul(g1_gen(), k), pt_mul(o2, k), pt_mul(g2_gen(), k)};
+}
+
+// make_new_tau_paramter (mpc.rs:677-706) on vector pair j: scalars (a x^i)^(+-1)
+bh_status new_tau_pair(bh_ctx* ctx, const Tables& tab, const MpcStorage* st, int j, const uint64_t a[4],
+                       const uint64_t x[4], int invert, MpcContrib* c) {
+  const bh_srs* g1 = st->v[2 * j].get();
+  const bh_srs* g2 = st->v[2 * j + 1].get();
+  DevBuf d_sc;
+  bh_status s = varbase_power_scalars(ctx, g1->n, a, x, invert, &d_sc);
+  if (s) return s;
+  const uint64_t one[4] = {1, 0, 0, 0};
+  const int stride = memcmp(x, one, 32) ? 8 : 0;  // x = 1: one scalar for the whole vector
+  for (int k = 0; k < 2; k++) {
+    c->res[2 * j + k].reset(new bh_srs());
+    c->mine[2 * j + k].reset(new bh_srs());
+  }
+  if ((s = varbase_mul(ctx, g1, d_sc.as<uint32_t>(), stride, 255, c->res[2 * j].get()))) return s;
+  if ((s = varbase_mul(ctx, g2, d_sc.as<uint32_t>(), stride, 255, c->res[2 * j + 1].get()))) return s;
+  if ((s = fixed_base_device<G1Ops>(ctx, tab.t1, d_sc.as<uint32_t>(), g1->n, BH_G1, c->mine[2 * j].get()))) return s;
+  return fixed_base_device<G2Ops>(ctx, tab.t2, d_sc.as<uint32_t>(), g1->n, BH_G2, c->mine[2 * j + 1].get());
+}
+
+// to_storage_format (mpc.rs:381-394, 910-923)
+template <class S>
+bh_status to_storage(bh_ctx* ctx, const MpcContrib* c, S** out) {
+  std::unique_ptr<S> n(new S());
+  n->ctx = ctx;
+  for (int k = 0; k < 2; k++) {
+    n->p1[k] = c->pp[k].r1;
+    n->p2[k] = c->pp[k].r2;
+  }
+  for (int k = 0; k < 6; k++) {
+    bh_status s = clone_srs(ctx, c->res[k].get(), &n->v[k]);
+    if (s) return s;
+  }
+  *out = n.release();
+  return BH_OK;
+}
+
+// ---------------------------------------------------------------- the verifier's side
+// verify_new_paramter (mpc.rs:787-804): e(R1, G2) == e(O1, M2) and e(R1, G2) == e(G1, R2)
+bool verify_pair(const HostPair& p, const AffinePt<Fp>& o1) {
+  const AffinePt<Fp2> ng2 = pt_neg(g2_gen());
+  return pairing_product_is_one({{p.r1, ng2}, {o1, p.m2}}) && pairing_product_is_one({{p.r1, ng2}, {g1_gen(), p.r2}});
+}
+
+bh_status msm_g1(bh_ctx* ctx, const bh_srs* b, const uint32_t* d_z, AffinePt<Fp>* out) {
+  Jac<Fp> r;
+  bh_status s = msm_g1_device(ctx, b, 0, d_z, b->n, nullptr, &r, nullptr);
+  if (!s) *out = jac_to_affine(r);
+  return s;
+}
+bh_status msm_g2(bh_ctx* ctx, const bh_srs* b, const uint32_t* d_z, AffinePt<Fp2>* out) {
+  Jac<Fp2> r;
+  bh_status s = msm_g2_device(ctx, b, 0, d_z, b->n, nullptr, &r, nullptr);
+  if (!s) *out = jac_to_affine(r);
+  return s;
+}
+
+// prod_i f(p_i, q_i): the Miller loops shared over the context's host pool, the partial Fp12
+// products multiplied
+Fp12 pooled_miller(bh_ctx* ctx, const std::vector<AffinePt<Fp>>& p, const std::vector<AffinePt<Fp2>>& q) {
+  HostPool& pool = ctx_pool(ctx);
+  const size_t n = p.size();
+  const int parts = (int)std::min<size_t>(n, (size_t)pool.size());
+  std::vector<Fp12> part((size_t)std::max(parts, 1), f12_one());
+  if (parts)
+    pool.parallel_for(parts, [&](int t) {
+      const size_t lo = n * (size_t)t / parts, hi = n * (size_t)(t + 1) / parts;
+      std::vector<Pair> ps;
+      ps.reserve(hi - lo);
+      for (size_t i = lo; i < hi; i++) ps.push_back({p[i], q[i]});
+      part[t] = multi_miller_loop(ps);
+    });
+  Fp12 f = f12_one();
+  for (const Fp12& x : part) f = f12_mul(f, x);
+  return f;
+}
+
+// One vector pair of verify_common_paramter (mpc.rs:842-854), batched with z:
+//   (1) e(S1, -G2) prod_i e(z_i O1_i, M2_i) == 1,  (2) e(S1, G2) == e(G1, S2),
+// S1 = sum z_i R1_i, S2 = sum z_i R2_i.  miller_ms: host wall time of the len Miller loops.
+bh_status verify_tau_pair(bh_ctx* ctx, const MpcStorage* st, const MpcContrib* c, int j, const uint32_t* d_z,
+                          int nbits, bool* ok, double* miller_ms) {
+  AffinePt<Fp> s1;
+  AffinePt<Fp2> s2;
+  bh_status s = msm_g1(ctx, c->res[2 * j].get(), d_z, &s1);
+  if (s) return s;
+  if ((s = msm_g2(ctx, c->res[2 * j + 1].get(), d_z, &s2))) return s;
+  bh_srs q;
+  if ((s = varbase_mul(ctx, st->v[2 * j].get(), d_z, 8, nbits, &q))) return s;
+  std::vector<AffinePt<Fp>> qh;
+  std::vector<AffinePt<Fp2>> m2;
+  if ((s = download_g1(&q, &qh))) return s;
+  if ((s = download_g2(c->mine[2 * j + 1].get(), &m2))) return s;
+  const AffinePt<Fp2> g2 = g2_gen(), ng2 = pt_neg(g2);
+  const auto t0 = std::chrono::steady_clock::now();
+  Fp12 f = pooled_miller(ctx, qh, m2);
+  if (miller_ms) *miller_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  f = f12_mul(f, multi_miller_loop({{s1, ng2}}));
+  *ok = f12_is_one(final_exponentiation(f)) && pairing_product_is_one({{s1, ng2}, {g1_gen(), s2}});
+  return BH_OK;
+}
+
+bh_status upload_z(bh_ctx* ctx, const uint64_t* z, size_t n, DevBuf* d_z, int* nbits) {
+  int nb = 1;
+  for (size_t i = 0; i < n; i++) {
+    if (!scalar_below_r(z + 4 * i) || scalar_is_zero(z + 4 * i)) return BH_ERR_INVALID_ARGUMENT;
+    nb = std::max(nb, scalar_bits(z + 4 * i));
+  }
+  *nbits = nb;
+  return varbase_upload_scalars(ctx, z, n, nb, d_z);
+}
+
+// ---------------------------------------------------------------- bytes
+void put_u32(std::vector<uint8_t>& v, size_t n) {
+  v.push_back((uint8_t)(n >> 24));
+  v.push_back((uint8_t)(n >> 16));
+  v.push_back((uint8_t)(n >> 8));
+  v.push_back((uint8_t)n);
+}
+void put_g1(std::vector<uint8_t>& v, const AffinePt<Fp>& p) {
+  uint8_t b[96];
+  g1_to_uncompressed(p, b);
+  v.insert(v.end(), b, b + 96);
+}
+void put_g2(std::vector<uint8_t>& v, const AffinePt<Fp2>& p) {
+  uint8_t b[192];
+  g2_to_uncompressed(p, b);
+  v.insert(v.end(), b, b + 192);
+}
+bh_status put_vec(std::vector<uint8_t>& v, const bh_srs* s) {
+  bh_status st;
+  if (s->group == BH_G1) {
+    std::vector<AffinePt<Fp>> h;
+    if ((st = download_g1(s, &h))) return st;
+    for (const auto& p : h) put_g1(v, p);
+  } else {
+    std::vector<AffinePt<Fp2>> h;
+    if ((st = download_g2(s, &h))) return st;
+    for (const auto& p : h) put_g2(v, p);
+  }
+  return BH_OK;
+}
+
+struct Reader {
+  const uint8_t* in;
+  size_t len, o = 0;
+  int checked;
+  bh_status u32(size_t* n) {
+    if (len - o < 4) return BH_ERR_UNEXPECTED_EOF;
+    *n = ((size_t)in[o] << 24) | ((size_t)in[o + 1] << 16) | ((size_t)in[o + 2] << 8) | in[o + 3];
+    o += 4;
+    return BH_OK;
+  }
+  bh_status g1(AffinePt<Fp>* p) {
+    if (len - o < 96) return BH_ERR_UNEXPECTED_EOF;
+    const int r = g1_from_uncompressed(in + o, p, checked != 0, checked != 0);
+    o += 96;
+    if (r == -3) return BH_ERR_NOT_IN_SUBGROUP;
+    if (r == -2) return BH_ERR_NOT_ON_CURVE;
+    return (r || p->infinity) ? BH_ERR_INVALID_ENCODING : BH_OK;
+  }
+  bh_status g2(AffinePt<Fp2>* p) {
+    if (len - o < 192) return BH_ERR_UNEXPECTED_EOF;
+    const int r = g2_from_uncompressed(in + o, p, checked != 0, checked != 0);
+    o += 192;
+    if (r == -3) return BH_ERR_NOT_IN_SUBGROUP;
+    if (r == -2) return BH_ERR_NOT_ON_CURVE;
+    return (r || p->infinity) ? BH_ERR_INVALID_ENCODING : BH_OK;
+  }
+  // n consecutive points of one group -> device vector (the checks of bh_params_load)
+  bh_status vec(bh_ctx* ctx, int group, size_t n, std::unique_ptr<bh_srs>* out) {
+    const size_t pb = group == BH_G1 ? 96 : 192;
+    if (n > (len - o) / pb) return BH_ERR_UNEXPECTED_EOF;
+    out->reset(new bh_srs());
+    const bh_status s = srs_from_bytes(ctx, group, in + o, n, checked, true, out->get());
+    o += n * pb;
+    return s;
+  }
+};
+
+// storage bytes.  common: u32-BE len, the four points, the six vectors; uncommon (vector pairs
+// of different lengths): the four points, then every vector behind its own u32-BE length
+bh_status storage_write(const MpcStorage* st, bool common, std::vector<uint8_t>& v) {
+  if (common) put_u32(v, st->v[0]->n);
+  for (int k = 0; k < 2; k++) {
+    put_g1(v, st->p1[k]);
+    put_g2(v, st->p2[k]);
+  }
+  for (int k = 0; k < 6; k++) {
+    if (!common) put_u32(v, st->v[k]->n);
+    bh_status s = put_vec(v, st->v[k].get());
+    if (s) return s;
+  }
+  return BH_OK;
+}
+
+template <class S>
+bh_status storage_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bool common, S** out) {
+  Reader r{bytes, len, 0, checked};
+  std::unique_ptr<S> st(new S());
+  st->ctx = ctx;
+  bh_status s;
+  size_t n = 0;
+  if (common && (s = r.u32(&n))) return s;
+  for (int k = 0; k < 2; k++) {
+    if ((s = r.g1(&st->p1[k])) || (s = r.g2(&st->p2[k]))) return s;
+  }
+  for (int k = 0; k < 6; k++) {
+    if (!common) {
+      size_t nk;
+      if ((s = r.u32(&nk))) return s;
+      if (k & 1) {
+        if (nk != n) return BH_ERR_INVALID_ENCODING;  // a pair's vectors have one length
+      } else {
+        n = nk;
+      }
+    }
+    if ((s = r.vec(ctx, k & 1 ? BH_G2 : BH_G1, n, &st->v[k]))) return s;
+  }
+  if (r.o != len) return BH_ERR_INVALID_ENCODING;
+  *out = st.release();
+  return BH_OK;
+}
+
+// contribution bytes: the ParameterPairs in declaration order (common: alpha, beta; uncommon:
+// delta, gamma), each g1_result, g2_result, g1_mine, g2_mine; then the three TauParameterPairs,
+// each a u32-BE length and that many ParameterPairs
+bh_status contrib_write(const MpcContrib* c, bool common, std::vector<uint8_t>& v) {
+  for (int k = 0; k < 2; k++) {
+    const HostPair& p = c->pp[common ? k : 1 - k];
+    put_g1(v, p.r1);
+    put_g2(v, p.r2);
+    put_g1(v, p.m1);
+    put_g2(v, p.m2);
+  }
+  for (int j = 0; j < 3; j++) {
+    std::vector<AffinePt<Fp>> r1, m1;
+    std::vector<AffinePt<Fp2>> r2, m2;
+    bh_status s;
+    if ((s = download_g1(c->res[2 * j].get(), &r1)) || (s = download_g2(c->res[2 * j + 1].get(), &r2)) ||
+        (s = download_g1(c->mine[2 * j].get(), &m1)) || (s = download_g2(c->mine[2 * j + 1].get(), &m2)))
+      return s;
+    put_u32(v, r1.size());
+    for (size_t i = 0; i < r1.size(); i++) {
+      put_g1(v, r1[i]);
+      put_g2(v, r2[i]);
+      put_g1(v, m1[i]);
+      put_g2(v, m2[i]);
+    }
+  }
+  return BH_OK;
+}
+
+template <class Cn>
+bh_status contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bool common, Cn** out) {
+  Reader r{bytes, len, 0, checked};
+  std::unique_ptr<Cn> c(new Cn());
+  c->ctx = ctx;
+  bh_status s;
+  for (int k = 0; k < 2; k++) {
+    HostPair& p = c->pp[common ? k : 1 - k];
+    if ((s = r.g1(&p.r1)) || (s = r.g2(&p.r2)) || (s = r.g1(&p.m1)) || (s = r.g2(&p.m2))) return s;
+  }
+  for (int j = 0; j < 3; j++) {
+    size_t n;
+    if ((s = r.u32(&n))) return s;
+    if (n > (len - r.o) / 576) return BH_ERR_UNEXPECTED_EOF;
+    // de-interleave the list into its four vectors
+    std::vector<uint8_t> col[4];
+    const size_t w[4] = {96, 192, 96, 192};
+    for (int k = 0; k < 4; k++) col[k].resize(n * w[k]);
+    for (size_t i = 0; i < n; i++) {
+      const uint8_t* b = bytes + r.o + i * 576;
+      size_t off = 0;
+      for (int k = 0; k < 4; k++) {
+        memcpy(&col[k][i * w[k]], b + off, w[k]);
+        off += w[k];
+      }
+    }
+    r.o += n * 576;
+    std::unique_ptr<bh_srs>* dst[4] = {&c->res[2 * j], &c->res[2 * j + 1], &c->mine[2 * j], &c->mine[2 * j + 1]};
+    for (int k = 0; k < 4; k++) {
+      dst[k]->reset(new bh_srs());
+      if ((s = srs_from_bytes(ctx, k & 1 ? BH_G2 : BH_G1, col[k].data(), n, checked, true, dst[k]->get()))) return s;
+    }
+  }
+  if (r.o != len) return BH_ERR_INVALID_ENCODING;
+  *out = c.release();
+  return BH_OK;
+}
+
+bh_status emit(const std::vector<uint8_t>& v, uint8_t* out, size_t cap, size_t* written) {
+  *written = v.size();
+  if (!out) return BH_OK;  // size query
+  if (cap < v.size()) return BH_ERR_INVALID_ARGUMENT;
+  memcpy(out, v.data(), v.size());
+  return BH_OK;
+}
+
+bh_status storage_point(const MpcStorage* st, int which, uint8_t* out) {
+  if (!st || !out || which < 0 || which > 3) return BH_ERR_INVALID_ARGUMENT;
+  if (which & 1)
+    g2_to_uncompressed(st->p2[which >> 1], out);
+  else
+    g1_to_uncompressed(st->p1[which >> 1], out);
+  return BH_OK;
+}
+bh_status contrib_point(const MpcContrib* c, int which, uint8_t* out) {
+  if (!c || !out || which < 0 || which > 7) return BH_ERR_INVALID_ARGUMENT;
+  const HostPair& p = c->pp[which >> 2];
+  switch (which & 3) {
+    case 0: g1_to_uncompressed(p.r1, out); break;
+    case 1: g2_to_uncompressed(p.r2, out); break;
+    case 2: g1_to_uncompressed(p.m1, out); break;
+    default: g2_to_uncompressed(p.m2, out); break;
+  }
+  return BH_OK;
+}
+bh_status contrib_vector(const MpcContrib* c, int which, int mine, const bh_srs** out) {
+  if (!c || !out || which < 0 || which > 5) return BH_ERR_INVALID_ARGUMENT;
+  *out = (mine ? c->mine : c->res)[which].get();
+  return BH_OK;
+}
+
+bh_status check_scalars(std::initializer_list<const uint64_t*> ws) {
+  for (const uint64_t* w : ws)
+    if (!w || !scalar_below_r(w)) return BH_ERR_INVALID_ARGUMENT;
+  for (const uint64_t* w : ws)
+    if (scalar_is_zero(w)) return BH_ERR_UNEXPECTED_IDENTITY;
+  return BH_OK;
+}
+
+struct CtxLock {
+  std::lock_guard<std::mutex> lk;
+  explicit CtxLock(bh_ctx* ctx) : lk(ctx->mu) {}
+};
+#define MPC_ENTER(ctx)                      \
+  CtxLock _lock(ctx);                       \
+  BH_TRY_HIP(hipSetDevice((ctx)->device)); \
+  if (bh_status _s = scratch_check(ctx)) return _s
+
+thread_local double g_miller_ms = 0;
+
+}  // namespace
+
+extern "C" {
+
+// ================================================================ round one
+bh_status bh_mpc_common_initial(bh_ctx* ctx, size_t len, bh_mpc_common** out) {
+  if (!ctx || !out || len > 0x7fffffffull) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  std::unique_ptr<bh_mpc_common> st(new bh_mpc_common());
+  st->ctx = ctx;
+  for (int k = 0; k < 2; k++) {
+    st->p1[k] = g1_gen();
+    st->p2[k] = g2_gen();
+  }
+  const std::vector<AffinePt<Fp>> v1(len, g1_gen());
+  const std::vector<AffinePt<Fp2>> v2(len, g2_gen());
+  bh_status s;
+  st->v[0].reset(new bh_srs());
+  st->v[1].reset(new bh_srs());
+  if ((s = srs_upload_affine(ctx, BH_G1, v1.data(), len, st->v[0].get()))) return s;
+  if ((s = srs_upload_affine(ctx, BH_G2, v2.data(), len, st->v[1].get()))) return s;
+  for (int k = 2; k < 6; k++)
+    if ((s = clone_srs(ctx, st->v[k & 1].get(), &st->v[k]))) return s;
+  *out = st.release();
+  return BH_OK;
+}
+
+bh_status bh_mpc_common_contribute(bh_ctx* ctx, const bh_mpc_common* st, const uint64_t alpha[4],
+                                   const uint64_t beta[4], const uint64_t tau[4], bh_mpc_common_contrib** out) {
+  if (!ctx || !st || !out || st->ctx->device != ctx->device) return BH_ERR_INVALID_ARGUMENT;
+  if (bh_status s = check_scalars({alpha, beta, tau})) return s;
+  MPC_ENTER(ctx);
+  std::unique_ptr<bh_mpc_common_contrib> c(new bh_mpc_common_contrib());
+  c->ctx = ctx;
+  c->pp[0] = new_pair(st->p1[0], st->p2[0], alpha);
+  c->pp[1] = new_pair(st->p1[1], st->p2[1], beta);
+  Tables tab;
+  bh_status s = tab.upload(ctx);
+  if (s) return s;
+  const uint64_t one[4] = {1, 0, 0, 0};
+  const uint64_t* a[3] = {one, alpha, beta};  // mpc.rs:756-776
+  for (int j = 0; j < 3; j++)
+    if ((s = new_tau_pair(ctx, tab, st, j, a[j], tau, 0, c.get()))) return s;
+  *out = c.release();
+  return BH_OK;
+}
+
+bh_status bh_mpc_common_verify(bh_ctx* ctx, const bh_mpc_common* st, const bh_mpc_common_contrib* c,
+                               const uint64_t* z, int* valid, bh_mpc_common** next) {
+  if (!ctx || !st || !c || !valid || !next) return BH_ERR_INVALID_ARGUMENT;
+  if (st->ctx->device != ctx->device || c->ctx->device != ctx->device) return BH_ERR_INVALID_ARGUMENT;
+  *valid = 0;
+  *next = nullptr;
+  const size_t len = st->v[0]->n;
+  if (len && !z) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  g_miller_ms = 0;
+  DevBuf d_z;
+  int nbits = 1;
+  bh_status s = upload_z(ctx, z, len, &d_z, &nbits);
+  if (s) return s;
+  // the reference's length check (mpc.rs:815-817), against the storage too: its loops index
+  // the storage's vectors with the contribution's length
+  for (int k = 0; k < 6; k++)
+    if (c->res[k]->n != len || c->mine[k]->n != len) return BH_OK;
+  bool ok = verify_pair(c->pp[0], st->p1[0]) && verify_pair(c->pp[1], st->p1[1]);
+  // alpha_mul_tau and beta_mul_tau (mpc.rs:842-854); the reference's check of the tau list
+  // itself is commented out (mpc.rs:831-840) and result_tau stays true
+  for (int j = 1; j < 3 && ok; j++)
+    if ((s = verify_tau_pair(ctx, st, c, j, d_z.as<uint32_t>(), nbits, &ok, &g_miller_ms))) return s;
+  if (!ok) return BH_OK;
+  if ((s = to_storage(ctx, c, next))) return s;
+  *valid = 1;
+  return BH_OK;
+}
+
+bh_status bh_mpc_common_h_basis(bh_ctx* ctx, const bh_mpc_common* st, size_t n, bh_srs** h_g1, bh_srs** h_g2) {
+  if (!ctx || !st || !h_g1 || !h_g2 || st->ctx->device != ctx->device) return BH_ERR_INVALID_ARGUMENT;
+  const size_t len = st->v[0]->n;
+  if (n > len / 2) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  std::unique_ptr<bh_srs> a(new bh_srs()), b(new bh_srs());
+  bh_status s;
+  if ((s = varbase_sub(ctx, st->v[0].get(), 0, n, n, a.get()))) return s;
+  if ((s = varbase_sub(ctx, st->v[1].get(), 0, n, n, b.get()))) return s;
+  *h_g1 = a.release();
+  *h_g2 = b.release();
+  return BH_OK;
+}
+
+size_t bh_mpc_common_len(const bh_mpc_common* st) { return st ? st->v[0]->n : 0; }
+bh_status bh_mpc_common_free(bh_mpc_common* st) {
+  delete st;
+  return BH_OK;
+}
+bh_status bh_mpc_common_contrib_free(bh_mpc_common_contrib* c) {
+  delete c;
+  return BH_OK;
+}
+bh_status bh_mpc_common_vector(const bh_mpc_common* st, int which, const bh_srs** out) {
+  if (!st || !out || which < 0 || which > 5) return BH_ERR_INVALID_ARGUMENT;
+  *out = st->v[which].get();
+  return BH_OK;
+}
+bh_status bh_mpc_common_point(const bh_mpc_common* st, int which, uint8_t* out) { return storage_point(st, which, out); }
+bh_status bh_mpc_common_contrib_vector(const bh_mpc_common_contrib* c, int which, int mine, const bh_srs** out) {
+  return contrib_vector(c, which, mine, out);
+}
+bh_status bh_mpc_common_contrib_point(const bh_mpc_common_contrib* c, int which, uint8_t* out) {
+  return contrib_point(c, which, out);
+}
+
+bh_status bh_mpc_common_write(const bh_mpc_common* st, uint8_t* out, size_t cap, size_t* written) {
+  if (!st || !written) return BH_ERR_INVALID_ARGUMENT;
+  std::vector<uint8_t> v;
+  {
+    CtxLock lk(st->ctx);
+    BH_TRY_HIP(hipSetDevice(st->ctx->device));
+    if (bh_status s = storage_write(st, true, v)) return s;
+  }
+  return emit(v, out, cap, written);
+}
+bh_status bh_mpc_common_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_mpc_common** out) {
+  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  return storage_read(ctx, bytes, len, checked, true, out);
+}
+bh_status bh_mpc_common_contrib_write(const bh_mpc_common_contrib* c, uint8_t* out, size_t cap, size_t* written) {
+  if (!c || !written) return BH_ERR_INVALID_ARGUMENT;
+  std::vector<uint8_t> v;
+  {
+    CtxLock lk(c->ctx);
+    BH_TRY_HIP(hipSetDevice(c->ctx->device));
+    if (bh_status s = contrib_write(c, true, v)) return s;
+  }
+  return emit(v, out, cap, written);
+}
+bh_status bh_mpc_common_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                     bh_mpc_common_contrib** out) {
+  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  return contrib_read(ctx, bytes, len, checked, true, out);
+}
+
+// ================================================================ round two
+bh_status bh_mpc_uncommon_initial(bh_ctx* ctx, const bh_srs* front_g1, const bh_srs* front_g2, const bh_srs* back_g1,
+                                  const bh_srs* back_g2, const bh_srs* h_g1, const bh_srs* h_g2,
+                                  bh_mpc_uncommon** out) {
+  if (!ctx || !out) return BH_ERR_INVALID_ARGUMENT;
+  const bh_srs* v[6] = {front_g1, front_g2, back_g1, back_g2, h_g1, h_g2};
+  for (int k = 0; k < 6; k++)
+    if (!same_device(ctx, v[k]) || v[k]->group != (k & 1 ? BH_G2 : BH_G1)) return BH_ERR_INVALID_ARGUMENT;
+  for (int j = 0; j < 3; j++)
+    if (v[2 * j]->n != v[2 * j + 1]->n) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  std::unique_ptr<bh_mpc_uncommon> st(new bh_mpc_uncommon());
+  st->ctx = ctx;
+  for (int k = 0; k < 2; k++) {
+    st->p1[k] = g1_gen();
+    st->p2[k] = g2_gen();
+  }
+  for (int k = 0; k < 6; k++)
+    if (bh_status s = clone_srs(ctx, v[k], &st->v[k])) return s;
+  *out = st.release();
+  return BH_OK;
+}
+
+bh_status bh_mpc_uncommon_contribute(bh_ctx* ctx, const bh_mpc_uncommon* st, const uint64_t gamma[4],
+                                     const uint64_t delta[4], bh_mpc_uncommon_contrib** out) {
+  if (!ctx || !st || !out || st->ctx->device != ctx->device) return BH_ERR_INVALID_ARGUMENT;
+  if (bh_status s = check_scalars({gamma, delta})) return s;
+  MPC_ENTER(ctx);
+  std::unique_ptr<bh_mpc_uncommon_contrib> c(new bh_mpc_uncommon_contrib());
+  c->ctx = ctx;
+  c->pp[0] = new_pair(st->p1[0], st->p2[0], gamma);
+  c->pp[1] = new_pair(st->p1[1], st->p2[1], delta);
+  Tables tab;
+  bh_status s = tab.upload(ctx);
+  if (s) return s;
+  const uint64_t one[4] = {1, 0, 0, 0};
+  const uint64_t* a[3] = {gamma, delta, delta};  // kin, kout, h: mpc.rs:1049-1054, inverted
+  for (int j = 0; j < 3; j++)
+    if ((s = new_tau_pair(ctx, tab, st, j, a[j], one, 1, c.get()))) return s;
+  *out = c.release();
+  return BH_OK;
+}
+
+bh_status bh_mpc_uncommon_verify(bh_ctx* ctx, const bh_mpc_uncommon* matrix, const bh_mpc_uncommon* st,
+                                 const bh_mpc_uncommon_contrib* c, const uint64_t* z, size_t z_len, int* valid,
+                                 bh_mpc_uncommon** next) {
+  if (!ctx || !matrix || !st || !c || !valid || !next) return BH_ERR_INVALID_ARGUMENT;
+  if (matrix->ctx->device != ctx->device || st->ctx->device != ctx->device || c->ctx->device != ctx->device)
+    return BH_ERR_INVALID_ARGUMENT;
+  *valid = 0;
+  *next = nullptr;
+  size_t maxlen = 0;
+  for (int j = 0; j < 3; j++) maxlen = std::max(maxlen, st->v[2 * j]->n);
+  if (z_len < maxlen || (maxlen && !z)) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  DevBuf d_z;
+  int nbits = 1;
+  bh_status s = upload_z(ctx, z, maxlen, &d_z, &nbits);
+  if (s) return s;
+  // the reference indexes the contribution's and the matrix' lists with the storage's lengths
+  // (mpc.rs:1089-1123)
+  for (int k = 0; k < 6; k++)
+    if (c->res[k]->n != st->v[k]->n || c->mine[k]->n != st->v[k]->n || matrix->v[k]->n != st->v[k]->n) return BH_OK;
+  bool ok = verify_pair(c->pp[1], st->p1[1]) && verify_pair(c->pp[0], st->p1[0]);  // delta, gamma: mpc.rs:1082-1086
+  const AffinePt<Fp2> ng2 = pt_neg(g2_gen());
+  for (int j = 0; j < 3 && ok; j++) {
+    // e(sum z_i new_i, gamma_or_delta_g2) == e(sum z_i matrix_i, G2)
+    AffinePt<Fp> sn, sm;
+    if ((s = msm_g1(ctx, c->res[2 * j].get(), d_z.as<uint32_t>(), &sn))) return s;
+    if ((s = msm_g1(ctx, matrix->v[2 * j].get(), d_z.as<uint32_t>(), &sm))) return s;
+    ok = pairing_product_is_one({{sn, c->pp[j == 0 ? 0 : 1].r2}, {sm, ng2}});
+  }
+  if (!ok) return BH_OK;
+  if ((s = to_storage(ctx, c, next))) return s;
+  *valid = 1;
+  return BH_OK;
+}
+
+bh_status bh_mpc_uncommon_free(bh_mpc_uncommon* st) {
+  delete st;
+  return BH_OK;
+}
+bh_status bh_mpc_uncommon_contrib_free(bh_mpc_uncommon_contrib* c) {
+  delete c;
+  return BH_OK;
+}
+bh_status bh_mpc_uncommon_vector(const bh_mpc_uncommon* st, int which, const bh_srs** out) {
+  if (!st || !out || which < 0 || which > 5) return BH_ERR_INVALID_ARGUMENT;
+  *out = st->v[which].get();
+  return BH_OK;
+}
+bh_status bh_mpc_uncommon_point(const bh_mpc_uncommon* st, int which, uint8_t* out) {
+  return storage_point(st, which, out);
+}
+bh_status bh_mpc_uncommon_contrib_vector(const bh_mpc_uncommon_contrib* c, int which, int mine, const bh_srs** out) {
+  return contrib_vector(c, which, mine, out);
+}
+bh_status bh_mpc_uncommon_contrib_point(const bh_mpc_uncommon_contrib* c, int which, uint8_t* out) {
+  return contrib_point(c, which, out);
+}
+bh_status bh_mpc_uncommon_write(const bh_mpc_uncommon* st, uint8_t* out, size_t cap, size_t* written) {
+  if (!st || !written) return BH_ERR_INVALID_ARGUMENT;
+  std::vector<uint8_t> v;
+  {
+    CtxLock lk(st->ctx);
+    BH_TRY_HIP(hipSetDevice(st->ctx->device));
+    if (bh_status s = storage_write(st, false, v)) return s;
+  }
+  return emit(v, out, cap, written);
+}
+bh_status bh_mpc_uncommon_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_mpc_uncommon** out) {
+  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  return storage_read(ctx, bytes, len, checked, false, out);
+}
+bh_status bh_mpc_uncommon_contrib_write(const bh_mpc_uncommon_contrib* c, uint8_t* out, size_t cap, size_t* written) {
+  if (!c || !written) return BH_ERR_INVALID_ARGUMENT;
+  std::vector<uint8_t> v;
+  {
+    CtxLock lk(c->ctx);
+    BH_TRY_HIP(hipSetDevice(c->ctx->device));
+    if (bh_status s = contrib_write(c, false, v)) return s;
+  }
+  return emit(v, out, cap, written);
+}
+bh_status bh_mpc_uncommon_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                       bh_mpc_uncommon_contrib** out) {
+  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  return contrib_read(ctx, bytes, len, checked, false, out);
+}
+
+// host wall time (ms) of the per-element Miller loops of this thread's last bh_mpc_common_verify
+double bh_mpc_last_miller_ms(void) { return g_miller_ms; }
+
+}  // extern "C"

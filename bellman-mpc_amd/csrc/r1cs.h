@@ -37,6 +37,12 @@ Jac<Fp2> crs_g2_gen();
 std::vector<AffinePt<Fp>> crs_table_g1();
 std::vector<AffinePt<Fp2>> crs_table_g2();
 
+// r1cs.hip: n canonical non-zero scalars on the device -> n packed affine points d_sc[i] * G through
+// crs.hip's fixed_base_batch, in chunks; tab: crs_table_g1 / _g2 on the device.  Synchronises
+// ctx->stream (caller holds ctx->mu)
+template <class C>
+bh_status fixed_base_device(bh_ctx* ctx, const bh_srs& tab, const uint32_t* d_sc, size_t n, int group, bh_srs* out);
+
 // api.hip: the ifft (domain.rs:104-121) of 2^L packed device-Montgomery Fr resident in d_a, natural
 // order in and out, d_tmp the same size; enqueued on ctx->stream (caller holds ctx->mu)
 bh_status device_ifft(bh_ctx* ctx, Domain* D, uint32_t* d_a, uint32_t* d_tmp);

@@ -131,6 +131,33 @@ void r1cs_kernels(std::vector<KernInfo>& v) {
   v.push_back({"k_r1cs_compact", (const void*)k_r1cs_compact, 256, 0});
 }
 
+// n canonical scalars on the device (all non-zero) -> packed affine points, in chunks as
+// chain.hip's fixed_base_to_srs; everything stream-ordered, the scratch shared by the chunks
+template <class C>
+bh_status fixed_base_device(bh_ctx* ctx, const bh_srs& tab, const uint32_t* d_sc, size_t n, int group, bh_srs* out) {
+  out->ctx = ctx;
+  out->group = group;
+  out->n = n;
+  out->identity_idx.clear();
+  const int words = group == BH_G1 ? 24 : 48;
+  BH_TRY_HIP(out->pts.alloc(std::max<size_t>(n, 1) * words * 4));
+  if (!n) return BH_OK;
+  const size_t chunk = std::min<size_t>(n, (size_t)1 << 21);
+  DevBuf d_xyzz, d_scr;
+  BH_TRY_HIP(d_xyzz.alloc(chunk * sizeof(typename C::P)));
+  BH_TRY_HIP(d_scr.alloc(chunk * sizeof(typename C::P) / 4 + 64));
+  for (size_t base = 0; base < n; base += chunk) {
+    const size_t k = std::min(chunk, n - base);
+    BH_TRY_HIP(fixed_base_batch<C>(tab.pts.as<uint32_t>(), d_sc + base * 8, k, d_xyzz.p, d_scr.p,
+                                   out->pts.as<uint32_t>() + base * words, ctx->stream));
+  }
+  BH_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the scratch is freed on return
+  return BH_OK;
+}
+
+template bh_status fixed_base_device<G1Ops>(bh_ctx*, const bh_srs&, const uint32_t*, size_t, int, bh_srs*);
+template bh_status fixed_base_device<G2Ops>(bh_ctx*, const bh_srs&, const uint32_t*, size_t, int, bh_srs*);
+
 }  // namespace bh
 
 namespace {
@@ -184,30 +211,6 @@ hipError_t qap_eval(const bh_r1cs* r, const uint32_t* d_x, uint32_t* d_part, uin
     hipLaunchKernelGGL(k_r1cs_long, dim3((unsigned)r->nlong), dim3(64), 0, st, r->longcols.as<uint32_t>(),
                        r->colseg.as<uint32_t>(), d_part, d_y);
   return hipGetLastError();
-}
-
-// n canonical scalars on the device (all non-zero) -> packed affine points, in chunks as
-// chain.hip's fixed_base_to_srs; everything stream-ordered, the scratch shared by the chunks
-template <class C>
-bh_status fixed_base_device(bh_ctx* ctx, const bh_srs& tab, const uint32_t* d_sc, size_t n, int group, bh_srs* out) {
-  out->ctx = ctx;
-  out->group = group;
-  out->n = n;
-  out->identity_idx.clear();
-  const int words = group == BH_G1 ? 24 : 48;
-  BH_TRY_HIP(out->pts.alloc(std::max<size_t>(n, 1) * words * 4));
-  if (!n) return BH_OK;
-  const size_t chunk = std::min<size_t>(n, (size_t)1 << 21);
-  DevBuf d_xyzz, d_scr;
-  BH_TRY_HIP(d_xyzz.alloc(chunk * sizeof(typename C::P)));
-  BH_TRY_HIP(d_scr.alloc(chunk * sizeof(typename C::P) / 4 + 64));
-  for (size_t base = 0; base < n; base += chunk) {
-    const size_t k = std::min(chunk, n - base);
-    BH_TRY_HIP(fixed_base_batch<C>(tab.pts.as<uint32_t>(), d_sc + base * 8, k, d_xyzz.p, d_scr.p,
-                                   out->pts.as<uint32_t>() + base * words, ctx->stream));
-  }
-  BH_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the scratch is freed on return
-  return BH_OK;
 }
 
 struct Matrix {

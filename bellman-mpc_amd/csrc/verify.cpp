@@ -15,17 +15,14 @@
 #include <vector>
 
 #include "api_internal.h"
+#include "pairing.h"
 
 using namespace bh;
 
-namespace {
+namespace bh {
 
 // ---------------------------------------------------------------- Fp12 = Fp2[w]/(w^6 - xi)
-struct Fp12 {
-  Fp2 c[6];
-};
-
-inline Fp2 mul_xi(const Fp2& a) {  // (a0 + a1 u)(1 + u), u^2 = -1
+static inline Fp2 mul_xi(const Fp2& a) {  // (a0 + a1 u)(1 + u), u^2 = -1
   return Fp2{sub(a.c0, a.c1), add(a.c0, a.c1)};
 }
 
@@ -60,7 +57,7 @@ Fp12 f12_mul(const Fp12& a, const Fp12& b) {
 }
 
 // (p^12 - 1) / r, little-endian 64-bit words (4314 bits), computed exactly (p, r of BLS12-381)
-const uint64_t FINAL_EXP[68] = {
+static const uint64_t FINAL_EXP[68] = {
     0xc0bcb9b55df57510ull, 0x25f98630e68bfb24ull, 0x4406fbc8fbd5f489ull, 0x8e2f8491d12191a0ull,
     0x3e9d71650a6f8069ull, 0x226c2f011d4cab80ull, 0x67f67c4717489119ull, 0xaf3f881bd88592d7ull,
     0x1a67e49eeed2161dull, 0xe5b78c7869aeb218ull, 0xf6539314043f7bbcull, 0x73f62537f2701aaeull,
@@ -95,11 +92,11 @@ Fp12 final_exponentiation(const Fp12& f) {
 }
 
 // ---------------------------------------------------------------- Miller loop
-constexpr uint64_t X_ABS = 0xd201000000010000ull;
+static constexpr uint64_t X_ABS = 0xd201000000010000ull;
 
 // line through T with slope lam (twist coordinates) at P, times w^3:
 // (lam*xt - yt) - lam*xp w^2 + yp w^3
-Fp12 line(const Fp2& lam, const Fp2& xt, const Fp2& yt, const AffinePt<Fp>& p) {
+static Fp12 line(const Fp2& lam, const Fp2& xt, const Fp2& yt, const AffinePt<Fp>& p) {
   Fp12 l;
   for (auto& x : l.c) x = Fp2::zero();
   l.c[0] = sub(mul(lam, xt), yt);
@@ -107,11 +104,6 @@ Fp12 line(const Fp2& lam, const Fp2& xt, const Fp2& yt, const AffinePt<Fp>& p) {
   l.c[3] = Fp2{p.y, Fp::zero()};
   return l;
 }
-
-struct Pair {
-  AffinePt<Fp> p;
-  AffinePt<Fp2> q;
-};
 
 Fp12 multi_miller_loop(const std::vector<Pair>& pairs) {
   std::vector<Pair> terms;
@@ -147,6 +139,10 @@ Fp12 multi_miller_loop(const std::vector<Pair>& pairs) {
 bool pairing_product_is_one(const std::vector<Pair>& pairs) {
   return f12_is_one(final_exponentiation(multi_miller_loop(pairs)));
 }
+
+}  // namespace bh
+
+namespace {
 
 // ---------------------------------------------------------------- decompression
 // big-integer exponents derived from p: (p + 1) / 4, (p - 3) / 4, (p - 1) / 2

@@ -21,6 +21,10 @@
  *                          create_proof after synthesis   groth16/prover.rs:206-349
  *   bh_r1cs_*              KeypairAssembly                groth16/generator.rs:44-156
  *   bh_generate_parameters generate_parameters            groth16/generator.rs:241-634
+ *   bh_srs_mul_each / _mul_powers / _sub_range
+ *                          make_new_tau_paramter, matrixed_h groth16/mpc.rs:677-706, 631-635
+ *   bh_mpc_common_*        the "common" ceremony round    groth16/mpc.rs:362-414, 708-862
+ *   bh_mpc_uncommon_*      the "uncommon" ceremony round  groth16/mpc.rs:891-1131
  *
  * Conventions
  *   - Plain pointers and sizes only; the caller owns every host buffer and the
@@ -407,6 +411,142 @@ bh_status bh_generate_parameters(bh_ctx* ctx, const bh_r1cs* r, const uint64_t a
                                  bh_params** out);
 /* The MiMC chain's KeypairAssembly (what bh_chain_params synthesizes internally) as a bh_r1cs. */
 bh_status bh_chain_r1cs(bh_ctx* ctx, size_t rounds, uint64_t seed, bh_r1cs** out);
+
+/* ---- per-element variable-base scalar multiplication: the primitive of a ceremony round
+ * (make_new_tau_paramter, groth16/mpc.rs:677-706).  Scalars are canonical Fr (4 LE u64 each);
+ * the result is a new bh_srs of the input's group and length (bh_srs_free it).
+ *   BH_ERR_INVALID_ARGUMENT     a scalar >= r (or wider than nbits), mismatched lengths, a range
+ *                               outside the vector
+ *   BH_ERR_UNEXPECTED_IDENTITY  a result that is the identity (a zero scalar, equal points in
+ *                               bh_srs_sub_range) or an identity among the inputs: a bh_srs these
+ *                               calls return never holds one
+ *   bh_srs_mul_each          out[i] = k_i * in[i], n == bh_srs_len(in)
+ *   bh_srs_mul_each_bounded  the same for scalars below 2^nbits (1..255; leading zero windows are
+ *                            skipped: a verifier's 128-bit z_i); n_scalars == bh_srs_len(in), or
+ *                            1: that one scalar multiplies every element
+ *   bh_srs_mul_powers        make_new_tau_paramter, mpc.rs:677-706: out[i] = (a * x^i)^(+-1) * in[i],
+ *                            inverted when invert != 0 ((a x^i)^-1 = a^-1 (x^-1)^i).  The reference
+ *                            forms x.pow(i) * a in u64; here it is formed in Fr, and the two agree
+ *                            whenever the reference's product does not overflow.
+ *   bh_srs_sub_range         out[i] = in[lo2 + i] - in[lo1 + i], i < n (mpc.rs:631-635) */
+bh_status bh_srs_mul_each(bh_ctx* ctx, const bh_srs* in, const uint64_t* scalars, size_t n, bh_srs** out);
+bh_status bh_srs_mul_each_bounded(bh_ctx* ctx, const bh_srs* in, const uint64_t* scalars, size_t n_scalars, int nbits,
+                                  bh_srs** out);
+bh_status bh_srs_mul_powers(bh_ctx* ctx, const bh_srs* in, const uint64_t a[4], const uint64_t x[4], int invert,
+                            bh_srs** out);
+bh_status bh_srs_sub_range(bh_ctx* ctx, const bh_srs* in, size_t lo1, size_t lo2, size_t n, bh_srs** out);
+
+/* ---- the MPC ceremony's parameter rounds (groth16/mpc.rs), for any length and any Fr scalar where
+ * the reference hard-codes length 8 and u64.  Handles belong to their context's device; toxic
+ * waste is canonical Fr (a word >= r: BH_ERR_INVALID_ARGUMENT, zero: BH_ERR_UNEXPECTED_IDENTITY).
+ *
+ * Round one, "common" parameters (mpc.rs:362-414, 708-862):
+ *   bh_mpc_common           CommonParamterInStorage (mpc.rs:398-414): alpha_g1/g2, beta_g1/g2 and
+ *                           tau, alpha_mul_tau, beta_mul_tau (g1, g2 each) as device vectors of one length
+ *   bh_mpc_common_contrib   CommonParamter (mpc.rs:362-373): g1_result, g2_result, g1_mine, g2_mine
+ *                           for alpha, beta and every element of the three vector pairs
+ *   bh_mpc_common_initial     initial_common_paramters         mpc.rs:708-728
+ *   bh_mpc_common_contribute  mpc_common_paramters_generator   mpc.rs:730-785
+ *   bh_mpc_common_verify      verify_common_paramter           mpc.rs:806-862.  z: len canonical
+ *                             nonzero scalars drawn at random by the caller (as bh_verify_batch's;
+ *                             128-bit ones suffice).  *valid = 1 and *next = the contribution's
+ *                             to_storage_format() (mpc.rs:381-394) when it verifies; else 0 and NULL,
+ *                             where the reference asserts.  The reference's per-element checks
+ *                             (verify_new_paramter, mpc.rs:787-804) run batched: per vector pair one
+ *                             multiexp of the results in each group, z_i * old_i on the device, len + 1
+ *                             Miller loops and one final exponentiation on the host; every contribution
+ *                             the reference accepts is accepted, one it rejects is accepted with
+ *                             probability about 2^-120.  Like the reference, whose
+ *                             check of the tau list is commented out (mpc.rs:831-840), it checks alpha,
+ *                             beta, alpha_mul_tau, beta_mul_tau and the lengths.
+ *   bh_mpc_common_h_basis     the matrixed_h part of matrix (mpc.rs:631-635): tau[n + i] - tau[i],
+ *                             i < n, in both groups; 2n > len: BH_ERR_INVALID_ARGUMENT.  The rest of
+ *                             matrix (list_mul_matrix) is the caller's.
+ *   bh_mpc_common_vector / _point, bh_mpc_common_contrib_vector / _point: borrowed views (valid while
+ *                             the handle lives; never bh_srs_free them) and uncompressed bytes
+ *   bh_mpc_common_write / _read, bh_mpc_common_contrib_write / _read: the reference keeps these structs
+ *                             in memory only; the bytes follow Parameters::write's conventions
+ *                             (mod.rs:224-290).  Storage: u32-BE len, then the fields in declaration
+ *                             order, G1 points uncompressed (96 B), G2 (192 B).  Contribution: the
+ *                             ParameterPairs of alpha and beta (g1_result, g2_result, g1_mine, g2_mine),
+ *                             then each TauParameterPair as u32-BE len and its ParameterPairs.  out ==
+ *                             NULL queries the size.  checked: the on-curve and subgroup checks of
+ *                             bh_params_load; the identity is refused either way.
+ * Round two, "uncommon" parameters (mpc.rs:891-1131): UnCommonParamterInStorage (gamma_g1/g2,
+ * delta_g1/g2, kin, kout, h) and UnCommonParamter (delta, gamma, ic, l, h).
+ *   bh_mpc_uncommon_initial     initial_uncommon_paramters (mpc.rs:993-1015) from the six vectors of
+ *                               CommonParamterMatrix (copied); a pair's lengths must agree
+ *   bh_mpc_uncommon_contribute  mpc_uncommon_paramters_generator (mpc.rs:1017-1063): kin by 1/gamma,
+ *                               kout and h by 1/delta
+ *   bh_mpc_uncommon_verify      verify_uncommon_paramter (mpc.rs:1065-1131).  matrix: the handle
+ *                               bh_mpc_uncommon_initial returned (it holds CommonParamterMatrix);
+ *                               z: z_len >= the longest vector's length.  The per-element checks share
+ *                               a G2 element on each side and collapse to
+ *                               e(sum z_i new_i, gamma_or_delta_g2) == e(sum z_i matrix_i, G2).
+ *   bytes: the four points, then each vector behind its own u32-BE length; the contribution as in
+ *   round one with the ParameterPairs in the order delta, gamma. */
+typedef struct bh_mpc_common bh_mpc_common;
+typedef struct bh_mpc_common_contrib bh_mpc_common_contrib;
+typedef struct bh_mpc_uncommon bh_mpc_uncommon;
+typedef struct bh_mpc_uncommon_contrib bh_mpc_uncommon_contrib;
+/* vectors of a storage / contribution (_vector's `which`) */
+#define BH_MPC_TAU_G1 0
+#define BH_MPC_TAU_G2 1
+#define BH_MPC_ALPHA_TAU_G1 2
+#define BH_MPC_ALPHA_TAU_G2 3
+#define BH_MPC_BETA_TAU_G1 4
+#define BH_MPC_BETA_TAU_G2 5
+#define BH_MPC_KIN_G1 0
+#define BH_MPC_KIN_G2 1
+#define BH_MPC_KOUT_G1 2
+#define BH_MPC_KOUT_G2 3
+#define BH_MPC_H_G1 4
+#define BH_MPC_H_G2 5
+/* points of a storage (_point's `which`): common alpha_g1, alpha_g2, beta_g1, beta_g2; uncommon
+ * gamma_g1, gamma_g2, delta_g1, delta_g2.  Of a contribution: 4 * pair + {0 g1_result, 1 g2_result,
+ * 2 g1_mine, 3 g2_mine}, pair 0 = alpha / gamma, 1 = beta / delta.  Even: 96 B, odd: 192 B. */
+bh_status bh_mpc_common_initial(bh_ctx* ctx, size_t len, bh_mpc_common** out);
+bh_status bh_mpc_common_contribute(bh_ctx* ctx, const bh_mpc_common* storage, const uint64_t alpha[4],
+                                   const uint64_t beta[4], const uint64_t tau[4], bh_mpc_common_contrib** out);
+bh_status bh_mpc_common_verify(bh_ctx* ctx, const bh_mpc_common* storage, const bh_mpc_common_contrib* contrib,
+                               const uint64_t* z, int* valid, bh_mpc_common** next);
+bh_status bh_mpc_common_h_basis(bh_ctx* ctx, const bh_mpc_common* storage, size_t n, bh_srs** h_g1, bh_srs** h_g2);
+size_t bh_mpc_common_len(const bh_mpc_common* storage);
+bh_status bh_mpc_common_free(bh_mpc_common* storage);
+bh_status bh_mpc_common_vector(const bh_mpc_common* storage, int which, const bh_srs** out);
+bh_status bh_mpc_common_point(const bh_mpc_common* storage, int which, uint8_t* out);
+bh_status bh_mpc_common_write(const bh_mpc_common* storage, uint8_t* out, size_t cap, size_t* written);
+bh_status bh_mpc_common_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_mpc_common** out);
+bh_status bh_mpc_common_contrib_free(bh_mpc_common_contrib* contrib);
+bh_status bh_mpc_common_contrib_vector(const bh_mpc_common_contrib* contrib, int which, int mine, const bh_srs** out);
+bh_status bh_mpc_common_contrib_point(const bh_mpc_common_contrib* contrib, int which, uint8_t* out);
+bh_status bh_mpc_common_contrib_write(const bh_mpc_common_contrib* contrib, uint8_t* out, size_t cap,
+                                      size_t* written);
+bh_status bh_mpc_common_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                     bh_mpc_common_contrib** out);
+bh_status bh_mpc_uncommon_initial(bh_ctx* ctx, const bh_srs* front_g1, const bh_srs* front_g2, const bh_srs* back_g1,
+                                  const bh_srs* back_g2, const bh_srs* h_g1, const bh_srs* h_g2,
+                                  bh_mpc_uncommon** out);
+bh_status bh_mpc_uncommon_contribute(bh_ctx* ctx, const bh_mpc_uncommon* storage, const uint64_t gamma[4],
+                                     const uint64_t delta[4], bh_mpc_uncommon_contrib** out);
+bh_status bh_mpc_uncommon_verify(bh_ctx* ctx, const bh_mpc_uncommon* matrix, const bh_mpc_uncommon* storage,
+                                 const bh_mpc_uncommon_contrib* contrib, const uint64_t* z, size_t z_len, int* valid,
+                                 bh_mpc_uncommon** next);
+bh_status bh_mpc_uncommon_free(bh_mpc_uncommon* storage);
+bh_status bh_mpc_uncommon_vector(const bh_mpc_uncommon* storage, int which, const bh_srs** out);
+bh_status bh_mpc_uncommon_point(const bh_mpc_uncommon* storage, int which, uint8_t* out);
+bh_status bh_mpc_uncommon_write(const bh_mpc_uncommon* storage, uint8_t* out, size_t cap, size_t* written);
+bh_status bh_mpc_uncommon_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_mpc_uncommon** out);
+bh_status bh_mpc_uncommon_contrib_free(bh_mpc_uncommon_contrib* contrib);
+bh_status bh_mpc_uncommon_contrib_vector(const bh_mpc_uncommon_contrib* contrib, int which, int mine,
+                                         const bh_srs** out);
+bh_status bh_mpc_uncommon_contrib_point(const bh_mpc_uncommon_contrib* contrib, int which, uint8_t* out);
+bh_status bh_mpc_uncommon_contrib_write(const bh_mpc_uncommon_contrib* contrib, uint8_t* out, size_t cap,
+                                        size_t* written);
+bh_status bh_mpc_uncommon_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                       bh_mpc_uncommon_contrib** out);
+/* host wall time (ms) the per-element Miller loops took in this thread's last bh_mpc_common_verify */
+double bh_mpc_last_miller_ms(void);
 
 /* Parameters::write of device-resident params (for parity tests; host copy). */
 bh_status bh_params_write(const bh_params* p, uint8_t* out, size_t cap, size_t* written);
