@@ -366,7 +366,7 @@ bh_status msm_g1_device(bh_ctx* ctx, const bh_srs* bases, size_t base_offset, co
   MsmShape sh = msm_shape(n, ctx->window_override);
   fit_segments<G1Ops>(sh, n);
   MsmTiming tm;
-  if (acc_ms) { tm.ev_acc_begin = ctx->ev[14]; tm.ev_acc_end = ctx->ev[15]; }
+  if (acc_ms) { tm.ev_acc_begin = ctx->ev[EV_MSM_ACC_BEGIN]; tm.ev_acc_end = ctx->ev[EV_MSM_ACC_END]; }
   BH_TRY_HIP(msm_window_sums<G1Ops>(ctx->g1ws, ctx->stream, bases->pts.as<uint32_t>(), d_scalars, n, d_idx,
                                     (uint32_t)base_offset, sh, acc_ms ? &tm : nullptr));
   BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
@@ -380,7 +380,7 @@ bh_status msm_g2_device(bh_ctx* ctx, const bh_srs* bases, size_t base_offset, co
   MsmShape sh = msm_shape(n, ctx->window_override);
   fit_segments<G2Ops>(sh, n);
   MsmTiming tm;
-  if (acc_ms) { tm.ev_acc_begin = ctx->ev[14]; tm.ev_acc_end = ctx->ev[15]; }
+  if (acc_ms) { tm.ev_acc_begin = ctx->ev[EV_MSM_ACC_BEGIN]; tm.ev_acc_end = ctx->ev[EV_MSM_ACC_END]; }
   BH_TRY_HIP(msm_window_sums<G2Ops>(ctx->g2ws, ctx->stream, bases->pts.as<uint32_t>(), d_scalars, n, d_idx,
                                     (uint32_t)base_offset, sh, acc_ms ? &tm : nullptr));
   BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
@@ -645,7 +645,7 @@ static bh_status host_fft(bh_ctx* ctx, uint64_t* coeffs, uint32_t log_m, FftKind
   BH_TRY_HIP(hipEventSynchronize(ctx->fft_ev[3]));
   for (int k = 0; k < 3; k++) {
     float t = 0;
-    ctx->last_timings[18 + k] = hipEventElapsedTime(&t, ctx->fft_ev[k], ctx->fft_ev[k + 1]) == hipSuccess ? t : -1;
+    ctx->last_timings[STAT_FFT_MS + k] = hipEventElapsedTime(&t, ctx->fft_ev[k], ctx->fft_ev[k + 1]) == hipSuccess ? t : -1;
   }
   return BH_OK;
 }

@@ -186,6 +186,9 @@ extern "C" void* scalar_pool_take(int device, size_t bytes, size_t* got);
 // selftest.hip (tests/test_gpu_selftest.py): fe2_mul_sub_kara and the two-product form on
 // caller-chosen operands
 extern "C" bh_status bh_selftest_fp2_mul_sub(int device, const uint32_t* in, size_t n, uint32_t* out);
+// prover.hip (tests/test_proof_schedule_cpu.py): proof_schedule() of proof_schedule.h on flat arrays
+extern "C" int bh_selftest_proof_schedule(const uint64_t* jobs, const uint8_t* rel, unsigned flags, int64_t* out,
+                                          size_t cap);
 struct bh_scalar_buf;
 // a device scalar vector of n canonical scalars (pooled), its ready event created
 extern "C" bh_status new_scalar_buf(bh_ctx* ctx, size_t n, std::shared_ptr<bh_scalar_buf>* out);
@@ -256,6 +259,35 @@ struct bh_witness {
   // the public inputs as canonical scalars on the host too (4 LE u64 each): the input
   // multiexps of a proof are a handful of terms and run on a host thread (prover.hip)
   std::vector<uint64_t> h_inputs;
+};
+
+// bh_ctx::jev, the prover's events of multiexp j = 0..7
+enum : int {
+  JEV_ACC_BEGIN = 0,     // + 2j: accumulate timing ...
+  JEV_ACC_END = 1,       // + 2j: ... its end
+  JEV_SORTED = 16,       // + j
+  JEV_ACCUMULATED = 24,  // + j
+  JEV_START = 32,        // the proof's start on the main stream
+  JEV_DENSITY = 33,      // density maps ready
+};
+// bh_ctx::ev
+enum : int {
+  EV_H_BEGIN = 0, EV_H_END = 1,  // the H block
+  EV_TAIL = 2,                   // + q: the tail of the q-th large multiexp, q = 0..7
+  // this proof's work on a stream is done: small multiexps, sorts, accumulations, H
+  EV_SMALL_DONE = 10, EV_SORTS_DONE = 11, EV_ACCS_DONE = 12, EV_H_DONE = 13,
+  EV_MSM_ACC_BEGIN = 14, EV_MSM_ACC_END = 15,  // bh_multiexp's accumulation timing (api.hip)
+};
+// bh_ctx::last_timings (the layout of bh_last_timings / bh_last_stats, include/bellman_hip.h)
+enum : int {
+  STAT_WALL_MS = 0, STAT_H_MS = 1,
+  STAT_G1_ACC_MS = 2, STAT_G1_LAUNCHES = 3, STAT_G1_PAIRS = 4,
+  STAT_G2_ACC_MS = 5, STAT_G2_LAUNCHES = 6, STAT_G2_PAIRS = 7,
+  STAT_G1_ADDS = 8, STAT_G2_ADDS = 9,
+  STAT_TABLES = 10, STAT_LARGE = 11, STAT_TABLE_BYTES = 12,
+  STAT_UP_AUX_MS = 13, STAT_UP_VEC_MS = 14 /* + v: a, b, c */, STAT_UP_H_END_MS = 17,  // bh_prove
+  STAT_FFT_MS = 18 /* + k: upload, transform, download */,                               // bh_fft & co.
+  STAT_G1_ACC_WALL_MS = 21, STAT_G2_ACC_WALL_MS = 22,
 };
 
 struct bh_ctx {

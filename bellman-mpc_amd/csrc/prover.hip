@@ -12,6 +12,7 @@
 #include "api_internal.h"
 #include "crs.h"
 #include "dist_h.h"
+#include "proof_schedule.h"
 
 using namespace bh;
 
@@ -345,8 +346,6 @@ inline void shard_range(size_t n, size_t k, size_t N, size_t* lo, size_t* hi) {
 // per (vector, c) -- a function of the CRS only, like Parameters::read -- and cost
 // n * ceil(256/c) points, each padded to whole 128-byte lines so one gather is one (G1)
 // or two (G2) lines (7 GB for a 2^22-point G1 vector at c = 20, 14 GB for b_g2).
-constexpr size_t SMALL_JOB = 4096;                   // run whole on a side stream (latency-bound)
-
 int table_c_for(size_t used_per_shard) {
   return used_per_shard >= TABLE_MIN_USED ? msm_table_c(used_per_shard) : 0;
 }
@@ -527,6 +526,11 @@ struct ShareGeom {
   size_t M = 0, C = 0;
   size_t used() const { return rank == N - 1 ? M - 1 : M; }
 };
+inline ShareGeom share_geom(int N, int rank, int L, size_t m) {
+  ShareGeom g;
+  g.N = N; g.rank = rank; g.L = L; g.M = m / N; g.C = g.M / N;
+  return g;
+}
 
 // h bases of a share, gathered into share order (built once per Parameters, N, rank, L)
 bh_status ensure_h_share(bh_ctx* ctx, bh_params* params, const ShareGeom& g, bh_srs** out) {
@@ -769,8 +773,6 @@ bool prover_serial() {  // (read per proof: tests/test_gpu_parity.py runs both m
 // the rank count qualifies, the H block is distributed (dist_h.h): this rank's h multiexp then
 // covers the share of h it ends with instead of the range [shard*(m-1)/N, ...).
 
-// `shard` of `nshards`: res1 = [h, l, a_inputs, a_aux, b_g1_inputs, b_g1_aux],
-// res2 = [b_g2_inputs, b_g2_aux].  Error checks cover the full (unsharded) query.
 // bh_prove_batch's pipelined lanes (set by the lane thread around one proof): after_accs once
 // the proof has enqueued everything but its reduction tails, before_tails / after_tails around
 // the tails' enqueue (proof order on the shared tail streams)
@@ -779,10 +781,508 @@ struct LaneHooks {
 };
 thread_local LaneHooks t_lane;
 
+// ---- error semantics (prover.rs:309-343 order: delta check, then the waits)
+bh_status check_queries(const bh_params* params, const bh_witness* w) {
+  const size_t m = w->m, ni = w->num_inputs, na = w->num_aux;
+  if (params->delta_g1.infinity || params->delta_g2.infinity) return BH_ERR_UNEXPECTED_IDENTITY;
+  // bases are validated at load (no identities), so only EOF is possible here
+  struct Q { const bh_srs* srs; size_t off; const std::vector<uint64_t>* dens; size_t n; };
+  const Q qs[] = {
+      {&params->a, 0, nullptr, ni},                          // a_inputs
+      {&params->a, ni, &w->a_aux_density, na},               // a_aux
+      {&params->b_g1, 0, &w->b_input_density, ni},           // b_g1_inputs
+      {&params->b_g1, w->b_in_total, &w->b_aux_density, na}, // b_g1_aux
+      {&params->b_g2, 0, &w->b_input_density, ni},           // b_g2_inputs
+      {&params->b_g2, w->b_in_total, &w->b_aux_density, na}, // b_g2_aux
+      {&params->h, 0, nullptr, m - 1},                       // h
+      {&params->l, 0, nullptr, na},                          // l
+  };
+  for (const Q& q : qs)
+    if (bh_status s = multiexp_check(q.srs, q.off, q.dens ? q.dens->data() : nullptr, q.n, nullptr, false)) return s;
+  return BH_OK;
+}
+
+// The proof reads the Parameters' window tables under a shared lock (prd, held on return) for its
+// whole duration; tables it wants but lacks are built first under the exclusive lock (a proof of
+// another shape may have replaced them), and the plan is made again under the shared one.
+struct ShardArgs {
+  size_t shard, nshards;
+  const ShareGeom* share;
+  const uint32_t* hbuf;
+  const int32_t *hidx, *idx_aaux, *idx_bin, *idx_baux;
+};
+bh_status plan_shard_locked(bh_ctx* ctx, const bh_params* params, const bh_witness* w, const ShardArgs& a,
+                            bool may_build, std::shared_lock<std::shared_mutex>& prd, Job jobs[8]) {
+  auto plan = [&](bool build) {
+    return plan_shard(ctx, params, w, a.shard, a.nshards, a.share, a.hbuf, a.hidx, a.idx_aaux, a.idx_bin, a.idx_baux,
+                      build, jobs);
+  };
+  bh_status s;
+  prd.lock();
+  if ((s = plan(false))) return s;
+  if (!may_build || !plan_needs_build(params, jobs, a.share, ctx->tables && !ctx->window_override)) return BH_OK;
+  prd.unlock();
+  {
+    std::unique_lock<std::shared_mutex> pwr(const_cast<bh_params*>(params)->mu);
+    if ((s = plan(true))) return s;
+  }
+  prd.lock();
+  return plan(false);
+}
+
+// The type-erased fields of one multiexp's workspace (pw1[out] or pw2[out]) that sorting, copying
+// and max_span need.  References: reserve_shape may move the buffers.
+struct WsView {
+  uint32_t *&entries, *&counts, *&offsets;
+  uint2*& recs2;
+  void* ws;
+  hipError_t (*reserve)(void*, size_t, const MsmShape&);
+  uint32_t* recs() const { return reinterpret_cast<uint32_t*>(recs2); }
+  hipError_t reserve_shape(size_t n, const MsmShape& sh) const { return reserve(ws, n, sh); }
+};
+template <class C>
+WsView ws_view_of(MsmWorkspace<C>& ws) {
+  return {ws.entries, ws.counts, ws.offsets, ws.recs, &ws, [](void* p, size_t n, const MsmShape& sh) {
+            return static_cast<MsmWorkspace<C>*>(p)->reserve_shape(n, sh);
+          }};
+}
+WsView ws_view(bh_ctx* ctx, const Job& J) { return J.g2 ? ws_view_of(ctx->pw2[J.out]) : ws_view_of(ctx->pw1[J.out]); }
+
+// the G1 / G2 template dispatch of a job's multiexp stages, on its own workspace
+void job_fit_segments(const Job& J, MsmShape& sh, size_t E) {
+  if (J.g2) fit_segments_E<G2Ops>(sh, E);
+  else fit_segments_E<G1Ops>(sh, E);
+}
+hipError_t job_sort(bh_ctx* ctx, const Job& J, hipStream_t st, size_t n, const MsmShape& sh) {
+  const int32_t* ix = J.idx ? J.idx + J.lo : nullptr;
+  const uint32_t* sc = J.sc + J.lo * 8;
+  return J.g2 ? msm_sort<G2Ops>(ctx->pw2[J.out], st, sc, n, ix, (uint32_t)J.lo, sh)
+              : msm_sort<G1Ops>(ctx->pw1[J.out], st, sc, n, ix, (uint32_t)J.lo, sh);
+}
+hipError_t job_accumulate(bh_ctx* ctx, const Job& J, hipStream_t st, const uint32_t* bases, size_t n,
+                          const MsmShape& sh, MsmTiming* tm) {
+  return J.g2 ? msm_accumulate<G2Ops>(ctx->pw2[J.out], st, bases, n, sh, tm)
+              : msm_accumulate<G1Ops>(ctx->pw1[J.out], st, bases, n, sh, tm);
+}
+hipError_t job_back(bh_ctx* ctx, const Job& J, hipStream_t st, size_t n, const MsmShape& sh, hipEvent_t acc_done,
+                    const uint32_t* dspan) {
+  return J.g2 ? msm_back<G2Ops>(ctx->pw2[J.out], st, n, sh, ctx->host_out2 + 128 * J.out, -1, acc_done, dspan)
+              : msm_back<G1Ops>(ctx->pw1[J.out], st, n, sh, ctx->host_out1 + 128 * J.out, -1, acc_done, dspan);
+}
+
+// One proof's multiexps as the setup leaves them: what the enqueue functions below work on.
+struct ProofRun {
+  bh_ctx* ctx = nullptr;
+  const bh_witness* w = nullptr;
+  Domain* D = nullptr;
+  Exchanger* ex = nullptr;
+  UploadSync* up = nullptr;
+  DistH* dh = nullptr;
+  Job jobs[8];
+  MsmShape shapes[8];
+  bool use_table[8] = {false};
+  int n_table = 0, n_large = 0;
+  hipStream_t streams[SCHED_STREAMS] = {};  // by SchedStream
+  size_t len(int j) const { return jobs[j].hi - jobs[j].lo; }
+};
+
+// the public-input multiexps of a proof on a host thread (host_input_msms)
+struct HostInputs {
+  std::thread th;
+  bh_status st = BH_OK;
+  Jac<Fp> a, b1;
+  Jac<bh::Fp2> b2;
+  ~HostInputs() { if (th.joinable()) th.join(); }
+};
+
+// density maps, inputs and aux of a witness that is still uploading (bh_prove), then the density
+// index maps (a resident witness carries them), all on the sort stream
+bh_status enqueue_density_maps(ProofRun& R, int32_t* idx_aaux, int32_t* idx_bin, int32_t* idx_baux) {
+  bh_ctx* ctx = R.ctx;
+  const bh_witness* w = R.w;
+  const size_t ni = w->num_inputs, na = w->num_aux;
+  hipStream_t sS = R.streams[SCHED_SORT];
+  if (UploadSync* up = R.up) {  // witness still uploading (bh_prove): density maps, inputs and aux first
+    if (!up->wait(1)) return up->status;
+    BH_TRY_HIP(hipStreamWaitEvent(sS, up->ev[0], 0));
+    if (w->raw) {  // bls12_381 Montgomery -> canonical scalars, here rather than on the copy stream
+      uint32_t* in = const_cast<uint32_t*>(w->inputs.as<uint32_t>());
+      uint32_t* ax = const_cast<uint32_t*>(w->aux.as<uint32_t>());
+      if (ni) BH_TRY_HIP(scalars_prepare(in, in, ni, 1, 0, sS));
+      if (na) BH_TRY_HIP(scalars_prepare(ax, ax, na, 1, 0, sS));
+    }
+  }
+  if (w->idx_ready) return BH_OK;
+  const uint64_t* d_a_aux = w->dens.as<uint64_t>();
+  const uint64_t* d_b_in = d_a_aux + w->a_aux_words;
+  const uint64_t* d_b_aux = d_b_in + w->b_in_words;
+  uint32_t *tmp = ctx->dtmp.as<uint32_t>(), *scan = ctx->dscan.as<uint32_t>();
+  if (na) BH_TRY_HIP(density_index(d_a_aux, na, (uint32_t)ni, idx_aaux, tmp, scan, sS));
+  if (ni) BH_TRY_HIP(density_index(d_b_in, ni, 0, idx_bin, tmp, scan, sS));
+  if (na) BH_TRY_HIP(density_index(d_b_aux, na, (uint32_t)w->b_in_total, idx_baux, tmp, scan, sS));
+  return BH_OK;
+}
+
+// each planned multiexp's shape: window table or plain windows, and its segment length
+bh_status job_shapes(ProofRun& R) {
+  for (int j = 0; j < 8; j++) {
+    const Job& J = R.jobs[j];
+    const size_t nj = R.len(j);
+    if (!nj) continue;
+    MsmShape& sh = R.shapes[j];
+    R.use_table[j] = J.table_c && J.srs->win_covers(J.table_c, J.blo, J.bhi);
+    if (J.bk_hi && !R.use_table[j]) {
+      // a bucket shard without its window table (HBM short when it was to be built): another rank
+      // may well have its table, so a plain-window stand-in here would not sum with the other
+      // ranks' parts -- refuse (bucket shards are opt-in, BH_SHARD_BUCKETS=1)
+      fprintf(stderr, "bellman_hip: bucket shard without its window table (HBM short): set BH_SHARD_BUCKETS=0\n");
+      return BH_ERR_OUT_OF_MEMORY;
+    }
+    sh = R.use_table[j] ? msm_shape_table(nj, J.srs->win_c) : msm_shape(nj, R.ctx->window_override);
+    if (R.use_table[j]) sh.rec = J.srs->win_rec;
+    if (J.bk_hi) {
+      sh.bk_lo = J.bk_lo;
+      sh.bk_hi = J.bk_hi;
+      // segments sized for the range's expected entries (the grid still covers every position)
+      const double f = bucket_cdf(sh.c, sh.W, sh.bk_hi) - bucket_cdf(sh.c, sh.W, sh.bk_lo);
+      job_fit_segments(J, sh, std::max<size_t>((size_t)((double)J.used * f), 1));
+    } else {
+      // segments sized for the entries the density set gives (the grid still covers n * W positions)
+      const size_t used_j = (size_t)((unsigned __int128)J.used * nj / std::max<size_t>(J.n, 1));
+      job_fit_segments(J, sh, seg_entries(nj, used_j, sh.W));
+    }
+    if (J.table_c) R.n_large++;
+    if (R.use_table[j]) R.n_table++;
+  }
+  return BH_OK;
+}
+
+// what j's sort can take from i's (SchedRel, proof_schedule.h)
+SchedRel sort_relation(const Job& I, const MsmShape& a, const Job& J, const MsmShape& b) {
+  if (I.sc != J.sc || I.lo != J.lo || I.hi != J.hi || a.c != b.c || a.W != b.W || a.NB != b.NB || a.Wb != b.Wb ||
+      a.pre != b.pre || a.bk_lo != b.bk_lo || a.bk_hi != b.bk_hi)
+    return SCHED_REL_NONE;
+  if (I.idx == J.idx) return SCHED_REL_SAME;
+  return !I.idx && J.idx && !I.is_h ? SCHED_REL_DERIVABLE : SCHED_REL_NONE;
+}
+
+SchedIn sched_input(const ProofRun& R, bool serial, bool host_in) {
+  SchedIn in;
+  for (int j = 0; j < 8; j++) {
+    const Job& J = R.jobs[j];
+    in.job[j] = SchedJob{R.len(j), J.used, R.len(j) ? R.shapes[j].W : 0, J.is_h, J.g2};
+    for (int i = 0; i < 8; i++)
+      if (i != j && R.len(i) && R.len(j)) in.rel[i][j] = sort_relation(R.jobs[i], R.shapes[i], J, R.shapes[j]);
+  }
+  in.serial = serial;
+  in.borrowed_streams = R.ctx->borrowed_streams;
+  in.cu_masked = R.ctx->cu_masked;
+  in.host_in = host_in;
+  in.uploading = R.up != nullptr;
+  in.distributed = R.dh != nullptr;
+  return in;
+}
+
+// ---- H (prover.rs:210-234), device resident.  Where it is enqueued: 'H placement' in
+// proof_schedule.h; only h's sort waits for it.
+bh_status enqueue_h(ProofRun& R) {
+  bh_ctx* ctx = R.ctx;
+  const bh_witness* w = R.w;
+  UploadSync* up = R.up;
+  hipStream_t sH = R.streams[SCHED_H];
+  if (up && up->on_vector) {
+    // bh_prove: the uploading thread enqueues H on sH vector by vector, each behind its own
+    // upload; only h's sort (enqueued on sH right after this) needs the host to wait until
+    // that enqueue is done
+    if (!up->wait(2)) return up->status;
+    return BH_OK;
+  }
+  BH_TRY_HIP(hipStreamWaitEvent(sH, ctx->jev[JEV_DENSITY], 0));
+  hipEventRecord(ctx->ev[EV_H_BEGIN], sH);
+  if (DistH* dh = R.dh) {  // three all-to-alls (RCCL, or the emulation's device copies), stream-ordered on sH
+    const size_t chunk = dh->C, M = dh->M;
+    Exchanger* ex = R.ex;
+    HExchange hx = [ex, chunk, M](const uint32_t* send, uint32_t* recv, int nvec, hipStream_t st) {
+      return ex->exchange(send, recv, chunk, M, nvec, st);
+    };
+    bh_status hs = dist_h_run(ctx, *dh, w->abc.as<uint32_t>(), hx, sH);
+    if (hs) return hs;
+    hipEventRecord(ctx->ev[EV_H_END], sH);
+    return BH_OK;
+  }
+  const size_t m = w->m;
+  uint32_t* abc = ctx->staging.as<uint32_t>();
+  if (up) {  // a, b, c still uploading (bh_prove)
+    if (!up->wait(2)) return up->status;
+    BH_TRY_HIP(hipStreamWaitEvent(sH, up->ev[1], 0));
+  }
+  const uint32_t* src = w->abc.as<uint32_t>();  // the first passes read the witness in place
+  if (w->raw) {  // convert into the H block's buffer (bls12_381 -> device Montgomery), zero padding
+    const size_t nc = w->num_constraints;
+    for (int v = 0; v < 3; v++) {
+      if (nc) launch_fr_convert(w->abc.as<uint32_t>() + (size_t)v * m * 8, abc + (size_t)v * m * 8, nc,
+                                fr_to_dev_const(), 0, sH);
+      if (m > nc) BH_TRY_HIP(hipMemsetAsync(abc + ((size_t)v * m + nc) * 8, 0, (m - nc) * 32, sH));
+    }
+    BH_TRY_HIP(hipGetLastError());
+    src = nullptr;
+  }
+  // ... and the last one writes h as canonical scalars in natural order, truncated to m-1
+  // (prover.rs:227-231)
+  bh_status hs = run_h_pipeline(ctx, R.D, abc, sH, src, ctx->hbuf.as<uint32_t>());
+  if (hs) return hs;
+  hipEventRecord(ctx->ev[EV_H_END], sH);
+  return BH_OK;
+}
+
+// A multiexp's sorted entries: its own sort, a copy of another multiexp's, or a compaction of a
+// dense one's (SchedRel), as the schedule decided; then its max-span words and its sorted event.
+bh_status sort_job(ProofRun& R, const SchedStep& step) {
+  bh_ctx* ctx = R.ctx;
+  const int j = step.job;
+  const Job& J = R.jobs[j];
+  const MsmShape& sh = R.shapes[j];
+  hipStream_t st = R.streams[step.stream];
+  const size_t n = R.len(j), nbt = (size_t)sh.Wb * sh.NB;
+  const WsView ws = ws_view(ctx, J);
+  if (step.wait_h) BH_TRY_HIP(hipStreamWaitEvent(st, ctx->ev[EV_H_END], 0));
+  if (step.kind == SCHED_SORT_REAL) {
+    BH_TRY_HIP(job_sort(ctx, J, st, n, sh));
+  } else {
+    const Job& S = R.jobs[step.src];
+    const WsView src = ws_view(ctx, S);
+    BH_TRY_HIP(ws.reserve_shape(n, sh));
+    if (step.kind == SCHED_SORT_DERIVE) {
+      const size_t Emax = n * (size_t)sh.W;
+      BH_TRY_HIP(ctx->dscan2.alloc(derive_scratch_words(Emax) * 4));
+      BH_TRY_HIP(hipStreamWaitEvent(st, ctx->jev[JEV_SORTED + step.src], 0));
+      BH_TRY_HIP(derive_sorted(src.entries, src.offsets, nbt, Emax, sh.pre, (uint32_t)sh.W, (uint32_t)S.lo,
+                               J.idx ? J.idx + J.lo : nullptr, ws.recs(), ctx->dscan2.as<uint32_t>(), ws.entries,
+                               ws.counts, ws.offsets, st, sh.bucket_shard() ? sh.bk_lo : 0u,
+                               sh.bucket_shard() ? sh.bk_hi : 0u));
+    } else {
+      BH_TRY_HIP(hipStreamWaitEvent(st, ctx->jev[JEV_SORTED + step.src], 0));
+      BH_TRY_HIP(hipMemcpyAsync(ws.counts, src.counts, (nbt + 1) * 4, hipMemcpyDeviceToDevice, st));
+      BH_TRY_HIP(hipMemcpyAsync(ws.offsets, src.offsets, (nbt + 1) * 4, hipMemcpyDeviceToDevice, st));
+      BH_TRY_HIP(hipMemcpyAsync(ws.entries, src.entries, n * (size_t)sh.W * 4, hipMemcpyDeviceToDevice, st));
+    }
+  }
+  // continuation-tree depth of this multiexp (read by its tail, so it launches only the
+  // levels that can do work)
+  // (a bucket shard: over its own buckets, the only ones its sort set)
+  BH_TRY_HIP(max_span(ws.counts + sh.red_lo(), ws.offsets + sh.red_lo(), (size_t)sh.Wb * sh.red_nb(), (uint32_t)sh.S,
+                      ctx->dspan.as<uint32_t>() + (size_t)j * MAX_SPAN_BLOCKS,
+                      ctx->host_spans + (size_t)j * MAX_SPAN_BLOCKS, st));
+  BH_TRY_HIP(hipEventRecord(ctx->jev[JEV_SORTED + j], st));
+  return BH_OK;
+}
+
+bh_status acc_job(ProofRun& R, const SchedStep& step) {
+  bh_ctx* ctx = R.ctx;
+  const int j = step.job;
+  const Job& J = R.jobs[j];
+  hipStream_t st = R.streams[step.stream];
+  if (step.wait_sorted >= 0) BH_TRY_HIP(hipStreamWaitEvent(st, ctx->jev[JEV_SORTED + step.wait_sorted], 0));
+  BH_TRY_HIP(hipStreamWaitEvent(st, ctx->jev[JEV_SORTED + j], 0));
+  MsmTiming tm;
+  tm.ev_acc_begin = acc_events_on() ? ctx->jev[JEV_ACC_BEGIN + 2 * j] : nullptr;
+  tm.ev_acc_end = acc_events_on() ? ctx->jev[JEV_ACC_END + 2 * j] : nullptr;
+  const uint32_t* bases = R.use_table[j] ? J.srs->win_global() : J.srs->pts.as<uint32_t>();
+  BH_TRY_HIP(job_accumulate(ctx, J, st, bases, R.len(j), R.shapes[j], &tm));
+  BH_TRY_HIP(hipEventRecord(ctx->jev[JEV_ACCUMULATED + j], st));
+  return BH_OK;
+}
+
+bh_status tail_job(ProofRun& R, const SchedStep& step) {
+  bh_ctx* ctx = R.ctx;
+  const int j = step.job;
+  const Job& J = R.jobs[j];
+  const MsmShape& sh = R.shapes[j];
+  hipStream_t st = R.streams[step.stream];
+  const size_t n = R.len(j);
+  BH_TRY_HIP(hipStreamWaitEvent(st, ctx->jev[JEV_ACCUMULATED + j], 0));
+  // entries = mixed additions of this multiexp (offsets[nbt]), for the VALU roofline
+  // (copied here, off the accumulation stream)
+  BH_TRY_HIP(hipMemcpyAsync(&ctx->host_counts[j], ws_view(ctx, J).offsets + (size_t)sh.Wb * sh.NB, 4,
+                            hipMemcpyDeviceToHost, st));
+  // The longest bucket span picks the continuation fold: the tail kernels read the sort's span
+  // words on the device, so enqueueing a tail never waits for its sort (a pipelined batch hands
+  // the streams on to the next proof without waiting for this one's h sort, which follows H)
+  const uint32_t* dspan = n >= SMALL_JOB ? ctx->dspan.as<uint32_t>() + (size_t)j * MAX_SPAN_BLOCKS : nullptr;
+  BH_TRY_HIP(job_back(ctx, J, st, n, sh, ctx->jev[JEV_ACCUMULATED + j], dspan));
+  if (step.slot >= 0) BH_TRY_HIP(hipEventRecord(ctx->ev[EV_TAIL + step.slot], st));
+  return BH_OK;
+}
+
+using HostClock = std::chrono::steady_clock;
+struct EnqueueTimes {
+  HostClock::time_point acc0, sorts, hand, enq;
+};
+
+// the executor: the schedule's steps, in order
+bh_status run_schedule(ProofRun& R, const ProofSchedule& P, EnqueueTimes* t) {
+  bh_ctx* ctx = R.ctx;
+  for (int i = 0; i < P.nsteps; i++) {
+    const SchedStep& step = P.steps[i];
+    bh_status s = BH_OK;
+    switch (step.op) {
+      case SCHED_OP_H: s = enqueue_h(R); break;
+      case SCHED_OP_SORT: s = sort_job(R, step); break;
+      case SCHED_OP_ACC: s = acc_job(R, step); break;
+      case SCHED_OP_TAIL: s = tail_job(R, step); break;
+      case SCHED_OP_MARK_ACC0: t->acc0 = HostClock::now(); break;
+      case SCHED_OP_MARK_SORTS: t->sorts = HostClock::now(); break;
+      case SCHED_OP_HANDOFF:
+        // The host waits of the collect phase are on events of THIS proof's work (not stream
+        // syncs): on a pipelined batch lane the streams soon hold the next proof's work behind it.
+        BH_TRY_HIP(hipEventRecord(ctx->ev[EV_SMALL_DONE], R.streams[SCHED_SMALL]));
+        BH_TRY_HIP(hipEventRecord(ctx->ev[EV_SORTS_DONE], R.streams[SCHED_SORT]));
+        BH_TRY_HIP(hipEventRecord(ctx->ev[EV_ACCS_DONE], R.streams[SCHED_MAIN]));
+        BH_TRY_HIP(hipEventRecord(ctx->ev[EV_H_DONE], R.streams[SCHED_H]));
+        // pipelined batch lanes: the next proof may enqueue its start-up and accumulations now (they
+        // queue behind these on every stream); this proof's tails go in only after the previous
+        // proof's (a tail stream would otherwise hold them behind the next proof's tails)
+        t->hand = HostClock::now();
+        if (t_lane.after_accs) t_lane.after_accs();
+        if (t_lane.before_tails) t_lane.before_tails();
+        break;
+    }
+    if (s) return s;
+  }
+  t->enq = HostClock::now();
+  if (t_lane.after_tails) t_lane.after_tails();
+  return BH_OK;
+}
+
+// the accumulations' totals per group ([0] G1, [1] G2), gathered while collecting
+struct AccTotals {
+  float ms[2] = {0, 0};
+  size_t pairs[2] = {0, 0}, adds[2] = {0, 0};
+  int launches[2] = {0, 0};
+};
+
+// Each multiexp's host combine runs as soon as its own tail stream is done (its window sums
+// are on the host), while later tails still run: only the last one's stays on the critical
+// path.  The small multiexps (the small stream) finish first.
+bh_status collect_results(ProofRun& R, const ProofSchedule& P, Jac<Fp> res1[6], Jac<bh::Fp2> res2[2], AccTotals* acc) {
+  bh_ctx* ctx = R.ctx;
+  for (int i = 0; i < 6; i++) res1[i] = jac_identity<Fp>();
+  for (int i = 0; i < 2; i++) res2[i] = jac_identity<bh::Fp2>();
+  for (int o = 0; o < P.nsmall + P.nbig; o++) {
+    const int j = o < P.nsmall ? P.small[o] : P.big[o - P.nsmall];
+    const Job& J = R.jobs[j];
+    if (o == 0 || o == P.nsmall) BH_TRY_HIP(hipEventSynchronize(ctx->ev[EV_SMALL_DONE]));
+    if (o >= P.nsmall) BH_TRY_HIP(hipEventSynchronize(ctx->ev[EV_TAIL + (o - P.nsmall)]));
+    float t = 0;
+    if (acc_events_on())
+      (void)hipEventElapsedTime(&t, ctx->jev[JEV_ACC_BEGIN + 2 * j], ctx->jev[JEV_ACC_END + 2 * j]);
+    if (J.g2) res2[J.out] = combine_g2(ctx->host_out2 + 128 * J.out, R.shapes[j]);
+    else res1[J.out] = combine_g1(ctx->host_out1 + 128 * J.out, R.shapes[j]);
+    acc->ms[J.g2] += t;
+    acc->launches[J.g2]++;
+    acc->pairs[J.g2] += (size_t)((unsigned __int128)J.used * R.len(j) / std::max<size_t>(J.n, 1));
+    acc->adds[J.g2] += ctx->host_counts[j];
+  }
+  for (int e = EV_SMALL_DONE; e <= EV_H_DONE; e++) BH_TRY_HIP(hipEventSynchronize(ctx->ev[e]));
+  return BH_OK;
+}
+
+// wall time during which at least one G1 (g2 = false) / G2 accumulation ran: the union of the
+// launches' event intervals
+double acc_wall_ms(const ProofRun& R, const ProofSchedule& P, bool g2) {
+  hipEvent_t* jev = R.ctx->jev;
+  std::vector<std::pair<float, float>> iv;
+  for (int q = 0; q < P.nbig; q++) {
+    const int j = P.big[q];
+    if (R.jobs[j].g2 != g2) continue;
+    float a = 0, b = 0;
+    if (hipEventElapsedTime(&a, jev[JEV_START], jev[JEV_ACC_BEGIN + 2 * j]) == hipSuccess &&
+        hipEventElapsedTime(&b, jev[JEV_START], jev[JEV_ACC_END + 2 * j]) == hipSuccess)
+      iv.push_back({a, b});
+  }
+  std::sort(iv.begin(), iv.end());
+  double tot = 0, cs = -1e30, ce = -1e30;
+  for (const auto& x : iv) {
+    if (x.first > ce) { if (ce > cs) tot += ce - cs; cs = x.first; ce = x.second; }
+    else ce = std::max(ce, (double)x.second);
+  }
+  if (ce > cs) tot += ce - cs;
+  return tot;
+}
+
+// bh_last_timings / bh_last_stats of one proof's multiexps
+void write_stats(const ProofRun& R, const ProofSchedule& P, const AccTotals& acc, double wall_ms) {
+  double* T = R.ctx->last_timings;
+  float h_ms = 0;
+  hipEventElapsedTime(&h_ms, R.ctx->ev[EV_H_BEGIN], R.ctx->ev[EV_H_END]);
+  T[STAT_WALL_MS] = wall_ms;
+  T[STAT_H_MS] = h_ms;
+  T[STAT_G1_ACC_MS] = acc.ms[0];
+  T[STAT_G1_LAUNCHES] = acc.launches[0];
+  T[STAT_G1_PAIRS] = (double)acc.pairs[0];
+  T[STAT_G2_ACC_MS] = acc.ms[1];
+  T[STAT_G2_LAUNCHES] = acc.launches[1];
+  T[STAT_G2_PAIRS] = (double)acc.pairs[1];
+  T[STAT_G1_ADDS] = (double)acc.adds[0];
+  T[STAT_G2_ADDS] = (double)acc.adds[1];
+  T[STAT_TABLES] = R.n_table;
+  T[STAT_LARGE] = R.n_large;
+  // with several accumulation lanes G1 launches overlap, so the summed launch time
+  // (STAT_G1_ACC_MS) counts that time twice: the wall time is their union
+  T[STAT_G1_ACC_WALL_MS] = acc_events_on() ? acc_wall_ms(R, P, false) : 0;
+  T[STAT_G2_ACC_WALL_MS] = acc_events_on() ? acc_wall_ms(R, P, true) : 0;
+  // bytes of the window tables this proof's multiexps read (each distinct table once): for a
+  // shard, its own slices and h share only, not whatever else the Parameters keep resident
+  size_t tb = 0;
+  for (int j = 0; j < 8; j++) {
+    if (!R.use_table[j]) continue;
+    bool seen = false;
+    for (int q = 0; q < j; q++) seen |= R.use_table[q] && R.jobs[q].srs == R.jobs[j].srs;
+    if (!seen) tb += R.jobs[j].srs->win->bytes;
+  }
+  T[STAT_TABLE_BYTES] = (double)tb;
+}
+
+// The streams of proof_schedule.h's SchedStream (BH_PROVER_SERIAL: all the main one), and the
+// proof's start on them.
+bh_status start_streams(ProofRun& R, bool serial) {
+  bh_ctx* ctx = R.ctx;
+  hipStream_t named[SCHED_TAIL0] = {ctx->stream, ctx->stream2, ctx->stream3, ctx->stream4, ctx->stream5};
+  for (int k = 0; k < SCHED_STREAMS; k++)
+    R.streams[k] = serial ? ctx->stream : k < SCHED_TAIL0 ? named[k] : ctx->tstream[k - SCHED_TAIL0];
+  BH_TRY_HIP(hipEventRecord(ctx->jev[JEV_START], R.streams[SCHED_MAIN]));
+  // ordered after whatever this context ran before on its main stream -- except on a pipelined
+  // batch lane (borrowed streams): there the main stream holds the previous proof's
+  // accumulations, which this proof's density maps and sorts must not wait for (they read only
+  // this lane's own witness and workspaces)
+  if (!ctx->borrowed_streams) {
+    BH_TRY_HIP(hipStreamWaitEvent(R.streams[SCHED_SORT], ctx->jev[JEV_START], 0));
+    BH_TRY_HIP(hipStreamWaitEvent(R.streams[SCHED_SMALL], ctx->jev[JEV_START], 0));
+  }
+  return BH_OK;
+}
+
+// BH_HOST_TIMING: the host's instants of one proof (H: the instant the first accumulation was enqueued)
+void print_host_timing(const bh_ctx* ctx, HostClock::time_point t0, const EnqueueTimes& te,
+                       HostClock::time_point t_gpu, HostClock::time_point t1) {
+  static const bool host_timing = getenv("BH_HOST_TIMING") != nullptr;
+  if (!host_timing) return;
+  auto ms = [](HostClock::time_point a, HostClock::time_point b) {
+    return std::chrono::duration<double, std::milli>(b - a).count();
+  };
+  fprintf(stderr, "compute_msms host: ctx %p start %.3f ms (monotonic), first accumulation enqueued %.3f ms, H %.3f, sorts %.3f, accumulations handed on %.3f, enqueue done %.3f, gpu and combines done %.3f, after %.3f\n",
+          (const void*)ctx, std::chrono::duration<double, std::milli>(t0.time_since_epoch()).count(), ms(t0, te.acc0),
+          ms(t0, te.acc0), ms(t0, te.sorts), ms(t0, te.hand), ms(t0, te.enq), ms(t0, t_gpu), ms(t_gpu, t1));
+}
+
+// `shard` of `nshards`: res1 = [h, l, a_inputs, a_aux, b_g1_inputs, b_g1_aux],
+// res2 = [b_g2_inputs, b_g2_aux].  Error checks cover the full (unsharded) query.
+// Setup (allocations, checks, the shard's plan under the Parameters' lock, the shapes), then the
+// schedule (proof_schedule.h) and its executor, then the host combines and the statistics.
 bh_status compute_msms(bh_ctx* ctx, const bh_params* params, const bh_witness* w, size_t shard, size_t nshards,
                        Jac<Fp> res1[6], Jac<bh::Fp2> res2[2], Exchanger* ex = nullptr, bool may_build = true,
                        UploadSync* up = nullptr) {
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = HostClock::now();
   if (bh_status sc = scratch_check(ctx)) return sc;  // rather than an abort inside the runtime
   bh_params* mparams = const_cast<bh_params*>(params);
   // The proof reads the Parameters' window tables under a shared lock (taken below).  Declared
@@ -800,8 +1300,9 @@ bh_status compute_msms(bh_ctx* ctx, const bh_params* params, const bh_witness* w
   const size_t m = w->m, ni = w->num_inputs, na = w->num_aux;
   const int L = w->log_m;
   bh_status s;
-  Domain* D;
-  if ((s = ctx_domain(ctx, L, &D))) return s;
+  ProofRun R;
+  R.ctx = ctx; R.w = w; R.ex = ex; R.up = up;
+  if ((s = ctx_domain(ctx, L, &R.D))) return s;
   const size_t maxn = std::max({m, ni, na, (size_t)1});
   BH_TRY_HIP(ctx->staging.alloc(3 * m * 32));
   BH_TRY_HIP(ctx->hbuf.alloc(m * 32));
@@ -809,64 +1310,11 @@ bh_status compute_msms(bh_ctx* ctx, const bh_params* params, const bh_witness* w
   BH_TRY_HIP(ctx->dtmp.alloc((maxn / 64 + 2) * 4));
   BH_TRY_HIP(ctx->dscan.alloc(scan_scratch_words(maxn / 64 + 2) * 4 + 64));
   BH_TRY_HIP(ctx->dspan.alloc(8 * MAX_SPAN_BLOCKS * 4));
-
-  // ---- error semantics (prover.rs:309-343 order: delta check, then the waits)
-  const uint64_t* dens = w->dens.as<uint64_t>();
-  const uint64_t* d_a_aux = dens;
-  const uint64_t* d_b_in = dens + w->a_aux_words;
-  const uint64_t* d_b_aux = dens + w->a_aux_words + w->b_in_words;
-  if (params->delta_g1.infinity || params->delta_g2.infinity) return BH_ERR_UNEXPECTED_IDENTITY;
-  {
-    // bases are validated at load (no identities), so only EOF is possible here
-    struct Q { const bh_srs* srs; size_t off; const std::vector<uint64_t>* dens; size_t n; };
-    const Q qs[] = {
-        {&params->a, 0, nullptr, ni},                          // a_inputs
-        {&params->a, ni, &w->a_aux_density, na},               // a_aux
-        {&params->b_g1, 0, &w->b_input_density, ni},           // b_g1_inputs
-        {&params->b_g1, w->b_in_total, &w->b_aux_density, na}, // b_g1_aux
-        {&params->b_g2, 0, &w->b_input_density, ni},           // b_g2_inputs
-        {&params->b_g2, w->b_in_total, &w->b_aux_density, na}, // b_g2_aux
-        {&params->h, 0, nullptr, m - 1},                       // h
-        {&params->l, 0, nullptr, na},                          // l
-    };
-    for (const Q& q : qs) {
-      s = multiexp_check(q.srs, q.off, q.dens ? q.dens->data() : nullptr, q.n, nullptr, false);
-      if (s) return s;
-    }
-  }
-  // Streams, all ordered after whatever ran before on ctx->stream:
-  //   stream    : the bucket accumulations back to back (VALU-bound critical path);
-  //   stream4   : the H pipeline (after the first accumulation, or first when distributed);
-  //   stream3   : density maps, then every multiexp's sort (memory-bound, runs ahead);
-  //   stream2   : the small (public-input) multiexps, whole;
-  //   tstream[q % 5]: the reduction tail of the q-th large multiexp.
-  // Each multiexp has its own workspace, so the only dependencies are the events below.
-  hipStream_t sA = ctx->stream, sT = ctx->stream2, sS = ctx->stream3, sH = ctx->stream4;
-  hipStream_t tails[8];
-  for (int q = 0; q < 8; q++) tails[q] = ctx->tstream[q % bh_ctx::TAIL_STREAMS];
+  if ((s = check_queries(params, w))) return s;
   const bool serial = prover_serial();
-  if (serial) {
-    sT = sS = sH = sA;
-    for (auto& t : tails) t = sA;
-  }
-  // The last multiexp's reduction tail runs when every accumulation is done, alone at the end of
-  // the critical path: on the CU-masked tail streams (a quarter of the CUs) its 2^19-bucket
-  // reduction needed two rounds of resident blocks.  So it runs on the
-  // small-multiexp stream (high priority, every CU), with its bucket reduction shaped for one round
-  // of the whole GPU (not on a pipelined batch lane, whose next proof's first accumulation would
-  // queue behind it).
-  const bool last_full = !serial && !ctx->borrowed_streams && ctx->cu_masked;
-  hipEvent_t* jev = ctx->jev;  // [2j,2j+1] accumulate timing, [16+j] sorted, [24+j] accumulated,
-                               // [32] start, [33] density maps ready
-  BH_TRY_HIP(hipEventRecord(jev[32], sA));
-  // ordered after whatever this context ran before on its main stream -- except on a pipelined
-  // batch lane (borrowed streams): there the main stream holds the previous proof's
-  // accumulations, which this proof's density maps and sorts must not wait for (they read only
-  // this lane's own witness and workspaces)
-  if (!ctx->borrowed_streams) {
-    BH_TRY_HIP(hipStreamWaitEvent(sS, jev[32], 0));
-    BH_TRY_HIP(hipStreamWaitEvent(sT, jev[32], 0));
-  }
+  if ((s = start_streams(R, serial))) return s;
+  hipStream_t sT = R.streams[SCHED_SMALL], sS = R.streams[SCHED_SORT], sH = R.streams[SCHED_H];
+  hipEvent_t* jev = ctx->jev;
 
   // ---- the 8 multiexps (prover.rs:233-307)
   // (a resident witness carries its maps from bh_witness_upload; bh_prove's is rebuilt per call)
@@ -875,39 +1323,16 @@ bh_status compute_msms(bh_ctx* ctx, const bh_params* params, const bh_witness* w
   int32_t* idx_bin = idx_aaux + na;
   int32_t* idx_baux = idx_bin + ni;
   // distributed H: this rank ends with its own share of h (dist_h.h), no range split
-  DistH* dh = nullptr;
   if (ex && dist_h_eligible((int)nshards, L) && nshards >= dist_h_min_ranks()) {
     if (!ctx->dist) ctx->dist = new DistH();
     if ((s = dist_h_init(ctx, *ctx->dist, (int)nshards, (int)shard, L))) return s;
-    dh = ctx->dist;
+    R.dh = ctx->dist;
   }
-  ShareGeom geom;
-  if (dh) {
-    geom.N = dh->N; geom.rank = dh->rank; geom.L = L; geom.M = dh->M; geom.C = dh->C;
-  }
-  const ShareGeom* sg = dh ? &geom : nullptr;
-  const uint32_t* sh_buf = dh ? dh->hbuf.as<uint32_t>() : nullptr;
-  const int32_t* sh_idx = dh ? dh->hidx.as<int32_t>() : nullptr;
-  // The proof reads the Parameters' window tables under a shared lock for its whole duration;
-  // tables it wants but lacks are built first under the exclusive lock (a proof of another
-  // shape may have replaced them).
-  Job jobs[8];
-  prd.lock();
-  if ((s = plan_shard(ctx, params, w, shard, nshards, sg, sh_buf, sh_idx, idx_aaux, idx_bin, idx_baux, false, jobs)))
-    return s;
-  if (may_build && plan_needs_build(params, jobs, sg, ctx->tables && !ctx->window_override)) {
-    prd.unlock();
-    {
-      std::unique_lock<std::shared_mutex> pwr(mparams->mu);
-      if ((s = plan_shard(ctx, params, w, shard, nshards, sg, sh_buf, sh_idx, idx_aaux, idx_bin, idx_baux, true,
-                          jobs)))
-        return s;
-    }
-    prd.lock();
-    if ((s = plan_shard(ctx, params, w, shard, nshards, sg, sh_buf, sh_idx, idx_aaux, idx_bin, idx_baux, false,
-                        jobs)))
-      return s;
-  }
+  const DistH* dh = R.dh;
+  const ShareGeom geom = dh ? share_geom(dh->N, dh->rank, L, m) : ShareGeom{};
+  const ShardArgs sa{shard, nshards, dh ? &geom : nullptr, dh ? dh->hbuf.as<uint32_t>() : nullptr,
+                     dh ? dh->hidx.as<int32_t>() : nullptr, idx_aaux, idx_bin, idx_baux};
+  if ((s = plan_shard_locked(ctx, params, w, sa, may_build, prd, R.jobs))) return s;
   // the public-input multiexps on a host thread (HOST_INPUT_MSM_MAX); BH_HOST_INPUTS=0: on the
   // device like the others (A/B experiments)
   // (read per proof: tests run the device branch of small input counts with BH_HOST_INPUTS=0)
@@ -915,526 +1340,41 @@ bh_status compute_msms(bh_ctx* ctx, const bh_params* params, const bh_witness* w
     const char* e = getenv("BH_HOST_INPUTS");
     return !(e && e[0] == '0');
   }();
-  const bool host_in = host_inputs_on && jobs[5].hi - jobs[5].lo <= HOST_INPUT_MSM_MAX;
-  struct HostInputs {
-    std::thread th;
-    bh_status st = BH_OK;
-    Jac<Fp> a, b1;
-    Jac<bh::Fp2> b2;
-    ~HostInputs() { if (th.joinable()) th.join(); }
-  } hin;
+  const bool host_in = host_inputs_on && R.len(5) <= HOST_INPUT_MSM_MAX;
+  HostInputs hin;
   if (host_in)
-    hin.th = std::thread([&hin, ctx, mparams, w, lo = jobs[5].lo, hi = jobs[5].hi] {
+    hin.th = std::thread([&hin, ctx, mparams, w, lo = R.jobs[5].lo, hi = R.jobs[5].hi] {
       hin.st = host_input_msms(ctx->device, mparams, w, lo, hi, &hin.a, &hin.b1, &hin.b2);
     });
-  if (up) {  // witness still uploading (bh_prove): density maps, inputs and aux first
-    if (!up->wait(1)) return up->status;
-    BH_TRY_HIP(hipStreamWaitEvent(sS, up->ev[0], 0));
-    if (w->raw) {  // bls12_381 Montgomery -> canonical scalars, here rather than on the copy stream
-      uint32_t* in = const_cast<uint32_t*>(w->inputs.as<uint32_t>());
-      uint32_t* ax = const_cast<uint32_t*>(w->aux.as<uint32_t>());
-      if (ni) BH_TRY_HIP(scalars_prepare(in, in, ni, 1, 0, sS));
-      if (na) BH_TRY_HIP(scalars_prepare(ax, ax, na, 1, 0, sS));
-    }
-  }
-  if (na && !w->idx_ready) BH_TRY_HIP(density_index(d_a_aux, na, (uint32_t)ni, idx_aaux, ctx->dtmp.as<uint32_t>(),
-                                   ctx->dscan.as<uint32_t>(), sS));
-  if (ni && !w->idx_ready)
-    BH_TRY_HIP(density_index(d_b_in, ni, 0, idx_bin, ctx->dtmp.as<uint32_t>(), ctx->dscan.as<uint32_t>(), sS));
-  if (na && !w->idx_ready) BH_TRY_HIP(density_index(d_b_aux, na, (uint32_t)w->b_in_total, idx_baux, ctx->dtmp.as<uint32_t>(),
-                                   ctx->dscan.as<uint32_t>(), sS));
-  MsmShape shapes[8];
-  bool use_table[8] = {false};
-  size_t los[8], his[8];
-  int n_table = 0, n_large = 0;
-  for (int j = 0; j < 8; j++) {
-    los[j] = jobs[j].lo;
-    his[j] = jobs[j].hi;
-    if (his[j] == los[j]) continue;
-    const bh_srs* srs = jobs[j].srs;
-    use_table[j] = jobs[j].table_c && srs->win_covers(jobs[j].table_c, jobs[j].blo, jobs[j].bhi);
-    if (jobs[j].bk_hi && !use_table[j]) {
-      // a bucket shard without its window table (HBM short when it was to be built): another rank
-      // may well have its table, so a plain-window stand-in here would not sum with the other
-      // ranks' parts -- refuse (bucket shards are opt-in, BH_SHARD_BUCKETS=1)
-      fprintf(stderr, "bellman_hip: bucket shard without its window table (HBM short): set BH_SHARD_BUCKETS=0\n");
-      return BH_ERR_OUT_OF_MEMORY;
-    }
-    shapes[j] = use_table[j] ? msm_shape_table(his[j] - los[j], srs->win_c)
-                             : msm_shape(his[j] - los[j], ctx->window_override);
-    if (use_table[j]) shapes[j].rec = srs->win_rec;
-    if (jobs[j].bk_hi) {
-      MsmShape& sh = shapes[j];
-      sh.bk_lo = jobs[j].bk_lo;
-      sh.bk_hi = jobs[j].bk_hi;
-      // segments sized for the range's expected entries (the grid still covers every position)
-      const double f = bucket_cdf(sh.c, sh.W, sh.bk_hi) - bucket_cdf(sh.c, sh.W, sh.bk_lo);
-      const size_t E = std::max<size_t>((size_t)((double)jobs[j].used * f), 1);
-      if (jobs[j].g2) fit_segments_E<G2Ops>(sh, E);
-      else fit_segments_E<G1Ops>(sh, E);
-    } else {
-      // segments sized for the entries the density set gives (the grid still covers n * W positions)
-      const size_t nj = his[j] - los[j];
-      const size_t used_j = (size_t)((unsigned __int128)jobs[j].used * nj / std::max<size_t>(jobs[j].n, 1));
-      const size_t E = seg_entries(nj, used_j, shapes[j].W);
-      if (jobs[j].g2) fit_segments_E<G2Ops>(shapes[j], E);
-      else fit_segments_E<G1Ops>(shapes[j], E);
-    }
-    if (jobs[j].table_c) n_large++;
-    if (use_table[j]) n_table++;
-  }
-  // ---- H (prover.rs:210-234), device resident.  Where it is enqueued: see 'H placement' below;
-  // only h's sort waits for it.
-  auto enqueue_h = [&](hipEvent_t after) -> bh_status {
-    if (up && up->on_vector) {
-      // bh_prove: the uploading thread enqueues H on sH vector by vector, each behind its own
-      // upload; only h's sort (enqueued on sH right after this) needs the host to wait until
-      // that enqueue is done
-      if (!up->wait(2)) return up->status;
-      return BH_OK;
-    }
-    BH_TRY_HIP(hipStreamWaitEvent(sH, after, 0));
-    hipEventRecord(ctx->ev[0], sH);
-    if (dh) {  // three all-to-alls (RCCL, or the emulation's device copies), stream-ordered on sH
-      const size_t chunk = dh->C, M = dh->M;
-      HExchange hx = [ex, chunk, M](const uint32_t* send, uint32_t* recv, int nvec, hipStream_t st) {
-        return ex->exchange(send, recv, chunk, M, nvec, st);
-      };
-      bh_status hs = dist_h_run(ctx, *dh, w->abc.as<uint32_t>(), hx, sH);
-      if (hs) return hs;
-      hipEventRecord(ctx->ev[1], sH);
-      return BH_OK;
-    }
-    uint32_t* abc = ctx->staging.as<uint32_t>();
-    if (up) {  // a, b, c still uploading (bh_prove)
-      if (!up->wait(2)) return up->status;
-      BH_TRY_HIP(hipStreamWaitEvent(sH, up->ev[1], 0));
-    }
-    const uint32_t* src = w->abc.as<uint32_t>();  // the first passes read the witness in place
-    if (w->raw) {  // convert into the H block's buffer (bls12_381 -> device Montgomery), zero padding
-      const size_t nc = w->num_constraints;
-      for (int v = 0; v < 3; v++) {
-        if (nc) launch_fr_convert(w->abc.as<uint32_t>() + (size_t)v * m * 8, abc + (size_t)v * m * 8, nc,
-                                  fr_to_dev_const(), 0, sH);
-        if (m > nc) BH_TRY_HIP(hipMemsetAsync(abc + ((size_t)v * m + nc) * 8, 0, (m - nc) * 32, sH));
-      }
-      BH_TRY_HIP(hipGetLastError());
-      src = nullptr;
-    }
-    // ... and the last one writes h as canonical scalars in natural order, truncated to m-1
-    // (prover.rs:227-231)
-    bh_status hs = run_h_pipeline(ctx, D, abc, sH, src, ctx->hbuf.as<uint32_t>());
-    if (hs) return hs;
-    hipEventRecord(ctx->ev[1], sH);
-    return BH_OK;
-  };
-  // Two multiexps with the same scalars, density map, range and digit geometry (b_g1_aux and
-  // b_g2_aux: prover.rs:282-307 both use the aux assignment under b_aux_density) have
-  // identical sorted entries, so the second one copies the first one's instead of sorting.
-  auto same_digits = [&](int i, int j) {
-    const MsmShape &a = shapes[i], &b = shapes[j];
-    return jobs[i].sc == jobs[j].sc && jobs[i].idx == jobs[j].idx && los[i] == los[j] && his[i] == his[j] &&
-           a.c == b.c && a.W == b.W && a.NB == b.NB && a.Wb == b.Wb && a.pre == b.pre && a.bk_lo == b.bk_lo &&
-           a.bk_hi == b.bk_hi;
-  };
-  // ... and one over a sparser density map (a_aux, b_aux under l's dense one) compacts it
-  auto derivable = [&](int i, int j) {
-    const MsmShape &a = shapes[i], &b = shapes[j];
-    return jobs[i].sc == jobs[j].sc && !jobs[i].idx && jobs[j].idx && !jobs[i].is_h && los[i] == los[j] &&
-           his[i] == his[j] && a.c == b.c && a.W == b.W && a.NB == b.NB && a.Wb == b.Wb && a.pre == b.pre &&
-           a.bk_lo == b.bk_lo && a.bk_hi == b.bk_hi;
-  };
-  int sorted_from[8];
-  for (int j = 0; j < 8; j++) sorted_from[j] = -1;
-  auto sort_job = [&](int j, hipStream_t st) -> bh_status {
-    const Job& J = jobs[j];
-    const size_t n = his[j] - los[j];
-    const int32_t* ix = J.idx ? J.idx + los[j] : nullptr;
-    const uint32_t* sc = J.sc + los[j] * 8;
-    int src = -1;
-    for (int i = 0; i < 8 && src < 0; i++)
-      if (i != j && sorted_from[i] == i && same_digits(i, j)) src = i;
-    int dsrc = -1;  // a fully dense sort over the same scalars and digits to compact from
-    for (int i = 0; i < 8 && src < 0 && dsrc < 0; i++)
-      if (i != j && sorted_from[i] == i && derivable(i, j)) dsrc = i;
-    if (dsrc >= 0) {
-      const MsmShape& sh = shapes[j];
-      const size_t nbt = (size_t)sh.Wb * sh.NB, Emax = n * (size_t)sh.W;
-      const auto& S = jobs[dsrc];
-      const uint32_t* se = S.g2 ? ctx->pw2[S.out].entries : ctx->pw1[S.out].entries;
-      const uint32_t* so = S.g2 ? ctx->pw2[S.out].offsets : ctx->pw1[S.out].offsets;
-      uint32_t *de, *dc, *dof, *pos;
-      if (J.g2) {
-        BH_TRY_HIP(ctx->pw2[J.out].reserve_shape(n, sh));
-        de = ctx->pw2[J.out].entries; dc = ctx->pw2[J.out].counts; dof = ctx->pw2[J.out].offsets;
-        pos = reinterpret_cast<uint32_t*>(ctx->pw2[J.out].recs);
-      } else {
-        BH_TRY_HIP(ctx->pw1[J.out].reserve_shape(n, sh));
-        de = ctx->pw1[J.out].entries; dc = ctx->pw1[J.out].counts; dof = ctx->pw1[J.out].offsets;
-        pos = reinterpret_cast<uint32_t*>(ctx->pw1[J.out].recs);
-      }
-      BH_TRY_HIP(ctx->dscan2.alloc(derive_scratch_words(Emax) * 4));
-      BH_TRY_HIP(hipStreamWaitEvent(st, jev[16 + dsrc], 0));
-      BH_TRY_HIP(derive_sorted(se, so, nbt, Emax, sh.pre, (uint32_t)sh.W, (uint32_t)los[dsrc], ix, pos,
-                               ctx->dscan2.as<uint32_t>(), de, dc, dof, st, sh.bucket_shard() ? sh.bk_lo : 0u,
-                               sh.bucket_shard() ? sh.bk_hi : 0u));
-      sorted_from[j] = j;  // a sort of its own from here on (copies may take it)
-    } else if (src >= 0) {
-      const MsmShape& sh = shapes[j];
-      const size_t nbt = (size_t)sh.Wb * sh.NB;
-      const uint32_t *e, *cn, *of;
-      if (jobs[src].g2) { e = ctx->pw2[jobs[src].out].entries; cn = ctx->pw2[jobs[src].out].counts; of = ctx->pw2[jobs[src].out].offsets; }
-      else { e = ctx->pw1[jobs[src].out].entries; cn = ctx->pw1[jobs[src].out].counts; of = ctx->pw1[jobs[src].out].offsets; }
-      uint32_t *de, *dc, *dof;
-      if (J.g2) {
-        BH_TRY_HIP(ctx->pw2[J.out].reserve_shape(n, sh));
-        de = ctx->pw2[J.out].entries; dc = ctx->pw2[J.out].counts; dof = ctx->pw2[J.out].offsets;
-      } else {
-        BH_TRY_HIP(ctx->pw1[J.out].reserve_shape(n, sh));
-        de = ctx->pw1[J.out].entries; dc = ctx->pw1[J.out].counts; dof = ctx->pw1[J.out].offsets;
-      }
-      BH_TRY_HIP(hipStreamWaitEvent(st, jev[16 + src], 0));
-      BH_TRY_HIP(hipMemcpyAsync(dc, cn, (nbt + 1) * 4, hipMemcpyDeviceToDevice, st));
-      BH_TRY_HIP(hipMemcpyAsync(dof, of, (nbt + 1) * 4, hipMemcpyDeviceToDevice, st));
-      BH_TRY_HIP(hipMemcpyAsync(de, e, n * (size_t)sh.W * 4, hipMemcpyDeviceToDevice, st));
-      sorted_from[j] = src;
-    } else {
-      if (J.g2) BH_TRY_HIP(msm_sort<G2Ops>(ctx->pw2[J.out], st, sc, n, ix, (uint32_t)los[j], shapes[j]));
-      else BH_TRY_HIP(msm_sort<G1Ops>(ctx->pw1[J.out], st, sc, n, ix, (uint32_t)los[j], shapes[j]));
-      sorted_from[j] = j;
-    }
-    // continuation-tree depth of this multiexp (read by its tail, so it launches only the
-    // levels that can do work)
-    const MsmShape& shj = shapes[j];
-    // (a bucket shard: over its own buckets, the only ones its sort set)
-    const uint32_t* cnt = (J.g2 ? ctx->pw2[J.out].counts : ctx->pw1[J.out].counts) + shj.red_lo();
-    const uint32_t* off = (J.g2 ? ctx->pw2[J.out].offsets : ctx->pw1[J.out].offsets) + shj.red_lo();
-    BH_TRY_HIP(max_span(cnt, off, (size_t)shj.Wb * shj.red_nb(), (uint32_t)shj.S,
-                        ctx->dspan.as<uint32_t>() + (size_t)j * MAX_SPAN_BLOCKS, ctx->host_spans + (size_t)j * MAX_SPAN_BLOCKS,
-                        st));
-    BH_TRY_HIP(hipEventRecord(jev[16 + j], st));
-    return BH_OK;
-  };
-  auto acc_job = [&](int j, hipStream_t st) -> bh_status {
-    const Job& J = jobs[j];
-    const size_t n = his[j] - los[j];
-    BH_TRY_HIP(hipStreamWaitEvent(st, jev[16 + j], 0));
-    MsmTiming tm;
-    tm.ev_acc_begin = acc_events_on() ? jev[2 * j] : nullptr;
-    tm.ev_acc_end = acc_events_on() ? jev[2 * j + 1] : nullptr;
-    const uint32_t* bases = use_table[j] ? J.srs->win_global() : J.srs->pts.as<uint32_t>();
-    if (J.g2) BH_TRY_HIP(msm_accumulate<G2Ops>(ctx->pw2[J.out], st, bases, n, shapes[j], &tm));
-    else BH_TRY_HIP(msm_accumulate<G1Ops>(ctx->pw1[J.out], st, bases, n, shapes[j], &tm));
-    BH_TRY_HIP(hipEventRecord(jev[24 + j], st));
-    return BH_OK;
-  };
-  auto tail_job = [&](int j, hipStream_t st) -> bh_status {
-    const Job& J = jobs[j];
-    const size_t n = his[j] - los[j];
-    BH_TRY_HIP(hipStreamWaitEvent(st, jev[24 + j], 0));
-    // entries = mixed additions of this multiexp (offsets[nbt]), for the VALU roofline
-    // (copied here, off the accumulation stream)
-    const uint32_t* offs = J.g2 ? ctx->pw2[J.out].offsets : ctx->pw1[J.out].offsets;
-    BH_TRY_HIP(hipMemcpyAsync(&ctx->host_counts[j], offs + (size_t)shapes[j].Wb * shapes[j].NB, 4,
-                              hipMemcpyDeviceToHost, st));
-    // The longest bucket span picks the continuation fold: the tail kernels read the sort's span
-    // words on the device, so enqueueing a tail never waits for its sort (a pipelined batch hands
-    // the streams on to the next proof without waiting for this one's h sort, which follows H)
-    const int span = -1;
-    const uint32_t* dspan = n >= SMALL_JOB ? ctx->dspan.as<uint32_t>() + (size_t)j * MAX_SPAN_BLOCKS : nullptr;
-    if (J.g2)
-      BH_TRY_HIP(msm_back<G2Ops>(ctx->pw2[J.out], st, n, shapes[j], ctx->host_out2 + 128 * J.out, span, jev[24 + j],
-                                 dspan));
-    else
-      BH_TRY_HIP(msm_back<G1Ops>(ctx->pw1[J.out], st, n, shapes[j], ctx->host_out1 + 128 * J.out, span, jev[24 + j],
-                                 dspan));
-    return BH_OK;
-  };
+  if ((s = enqueue_density_maps(R, idx_aaux, idx_bin, idx_baux))) return s;
+  if ((s = job_shapes(R))) return s;
   // the H stream follows the density maps and sorts enqueued so far -- unless the uploading
   // thread is enqueueing H on it vector by vector (bh_prove): those kernels are ordered behind
   // their uploads already, and a wait issued here would land between them at a random point
-  // (jev[33] = the density maps: the small multiexps' stream waits on it below)
-  BH_TRY_HIP(hipEventRecord(jev[33], sS));
-  if (!(up && up->on_vector)) BH_TRY_HIP(hipStreamWaitEvent(sH, jev[33], 0));
-  int big[8], nbig = 0, small[8], nsmall = 0;
-  hipStream_t acc_stream[8] = {};  // the stream each large multiexp's accumulation was enqueued on
-  for (int j = 0; j < 8; j++) {
-    const size_t n = his[j] - los[j];
-    if (!n || (host_in && j >= 5)) continue;
-    if (n < SMALL_JOB && !jobs[j].is_h) small[nsmall++] = j;
-    else big[nbig++] = j;
-  }
-  // Large ones: sorts run ahead on stream3, accumulations back to back on the main stream,
-  // each reduction tail on a stream of its own (the tails are latency-bound chains of point
-  // additions: several run side by side at little cost, and none waits behind another).
-  int h_pos = nbig;
-  for (int q = 0; q < nbig; q++)
-    if (jobs[big[q]].is_h) h_pos = q;
-  // (Tried and removed: the last multiexp accumulated and reduced as two bucket halves so the
-  // lower half's reduction runs beside the upper half's accumulation, +0.8 ms per 2^22 proof,
-  // profiles/r03_ab_last_halves.txt; fewer rounds for the last accumulation, within noise.)
-  // H placement.  A resident witness enqueues H first, running beside everything: since the G2
-  // accumulation keeps ZZ/ZZZ in LDS (268 registers, msm_impl.cuh accumulate_lds) H's NTT passes
-  // co-reside with it (same-box A/B at 2^22: 55.1-55.3 ms per proof against 57.4-58.2 with H after
-  // the first accumulation, profiles/r04_ab_hmode_g2.txt).  Other placements were measured and
-  // removed: H enqueued after the first accumulation's launch, between the first sorts and the first
-  // accumulation, from a helper host thread, or held on the device until the first sort is done
-  // (N = 8 rehearsal within 0.1 ms or slower, profiles/r03_ab_hmode_N8.txt, r03_ab_hmode_more_N8.txt,
-  // r05_ab_sched_knobs_N1_2_8.txt).  From host buffers (bh_prove) the uploading thread enqueues H
-  // vector by vector behind each upload (on_vector); here only h's own sort and accumulation wait on
-  // the host for that enqueue, so they are enqueued last.
-  bool h_late = up != nullptr;
+  // (JEV_DENSITY = the density maps: the small multiexps' stream waits on it too)
+  BH_TRY_HIP(hipEventRecord(jev[JEV_DENSITY], sS));
+  if (!(up && up->on_vector)) BH_TRY_HIP(hipStreamWaitEvent(sH, jev[JEV_DENSITY], 0));
   // the small multiexps run whole on their own stream, after the density maps
-  BH_TRY_HIP(hipStreamWaitEvent(sT, jev[33], 0));
-  auto run_small = [&]() -> bh_status {
-    for (int i = 0; i < nsmall; i++) {
-      bh_status e = sort_job(small[i], sT);
-      if (!e) e = acc_job(small[i], sT);
-      if (!e) e = tail_job(small[i], sT);
-      if (e) return e;
-    }
-    return BH_OK;
-  };
-  // Host enqueue order follows the critical path: the first two sorts (a sort running beside
-  // a whole-GPU accumulation only gets CUs as its workgroups retire, so the second one would
-  // not be ready when the first accumulation ends), the first accumulation, H, the remaining
-  // sorts (h's after H), every accumulation, the small multiexps, then the tails.
-  // Sort order = accumulation order (b_g2_aux sorted, b_g1_aux copied, l sorted, a_aux
-  // compacted from l, h): putting l first so that b_g2_aux could be compacted from it would
-  // lengthen the start-up (measured +2 ms at 2^22), so only later sorts are derived.
-  // h's digit sort reads the H block's output: on a replicated H it runs on the H stream right
-  // behind it, so the sort stream never waits for H (a pipelined batch's next proof queues its
-  // density maps and sorts there, behind this proof's); distributed H (CU-masked stream) keeps it
-  // on the sort stream after an event wait
-  auto sort_h_or = [&](int j) -> bh_status {
-    if (!jobs[j].is_h) return sort_job(j, sS);
-    if (!dh) return sort_job(j, sH);
-    BH_TRY_HIP(hipStreamWaitEvent(sS, ctx->ev[1], 0));
-    return sort_job(j, sS);
-  };
-  int sorder[8];
-  const int ns = nbig;
-  for (int q = 0; q < nbig; q++) sorder[q] = big[q];
-  // every sort up to those of the first two accumulations runs ahead of the first accumulation
-  int pre_sorts = 0;
-  for (int r = 0; r < ns; r++)
-    if (sorder[r] == big[0] || (nbig > 1 && h_pos != 1 && sorder[r] == big[1])) pre_sorts = r + 1;
-  bool h_in_pre = false;
-  for (int r = 0; r < pre_sorts; r++) h_in_pre = h_in_pre || jobs[sorder[r]].is_h;
-  if (h_in_pre) h_late = false;  // h's own sort is among the first: H first
-  if (!h_late && (s = enqueue_h(jev[33]))) return s;
+  BH_TRY_HIP(hipStreamWaitEvent(sT, jev[JEV_DENSITY], 0));
 
-  for (int r = 0; r < pre_sorts; r++) {
-    if ((s = sort_h_or(sorder[r]))) return s;
-  }
-  // The first accumulation (G2: 268 registers, one wave per SIMD) runs on the small-multiexp
-  // stream (idle when the public-input multiexps are on the host), so the G1 accumulations start
-  // beside it instead of after it: same-box A/B at 2^22 54.66-55.17 against 55.01-55.45 ms
-  // (profiles/r04_ab_first_acc_stream.txt).
-  const bool first_own = nsmall == 0 && !serial;
-  if (nbig > 0) {
-    // wait for the last pre-sort that is a real sort: a trailing copy of another multiexp's
-    // entries (b_g1_aux from b_g2_aux) is ~0.15 ms of blits that can run beside the accumulation
-    int wait_j = big[0];
-    for (int r = 0; r < pre_sorts; r++)
-      if (sorted_from[sorder[r]] == sorder[r]) wait_j = sorder[r];
-    hipStream_t s0 = first_own ? sT : sA;
-    BH_TRY_HIP(hipStreamWaitEvent(s0, jev[16 + wait_j], 0));
-    if ((s = acc_job(big[0], s0))) return s;
-    acc_stream[0] = s0;
-  }
-  // With the first accumulation on its own stream, the second one (G1: b_g1_aux, whose sorted
-  // entries are a copy among the first sorts) is enqueued right behind it, before the remaining
-  // sorts: those are ~20-40 host enqueues (~0.7 ms per rank at N = 8 in the round-5 kernel
-  // trace, 1.6 ms at N = 2), during which the G2 accumulation ran alone on its one wave per SIMD.
-  int q_first = 1;
-  if (nbig > 1 && !jobs[big[1]].is_h && first_own) {
-    bool pre = false;  // its sort is among the pre-sorts (enqueued above)
-    for (int r = 0; r < pre_sorts; r++) pre = pre || sorder[r] == big[1];
-    if (pre) {
-      if ((s = acc_job(big[1], sA))) return s;
-      acc_stream[1] = sA;
-      q_first = 2;
-    }
-  }
-  const auto t_acc0 = std::chrono::steady_clock::now();
-  const auto t_h = std::chrono::steady_clock::now();
-  for (int r = pre_sorts; r < ns; r++) {
-    if (h_late && jobs[sorder[r]].is_h) continue;  // behind H, enqueued below
-    if ((s = sort_h_or(sorder[r]))) return s;
-  }
-  const auto t_sorts = std::chrono::steady_clock::now();
-  // Accumulation lanes: the accumulations after the first two go to whichever of three accumulation
-  // streams (the first one's, the main one, stream5) has the least queued work (mixed additions, a G2
-  // one weighted 2.75x).  Consecutive accumulations on one stream are separated by a barrier (the
-  // next kernel dispatches only once the last block of the previous one is done: ~0.12 ms between
-  // them in the round-5 traces), and in that moment other streams' pending kernels take the freed
-  // slots (round-5 drop-in trace: 1.4 and 2.9 ms of main-stream idle before a_aux and h).  Two lanes
-  // (round 5): rehearsal N = 8 9.85-9.92 against 10.05-10.23 ms per rank (profiles/r05_ab_acc_lanes.txt);
-  // with the G2 accumulation holding one lane for most of the proof, the G1 ones still ran back to
-  // back on the other, so round 6 adds a third: the 2^22 bench 54.4-54.6 against 54.8-55.0 ms, bh_prove
-  // 58.7-58.9 against 59.5-59.7, N = 2 30.4 against 30.8-31.2 ms per rank, N = 1 and 8 within noise
-  // (profiles/r06_ab_acc_lanes3.txt).
-  const bool multi_lane = first_own && !ctx->borrowed_streams && nbig > 2;
-  auto acc_cost = [&](int j) {
-    const double e = (double)jobs[j].used * (double)(shapes[j].W ? shapes[j].W : 1);
-    return jobs[j].g2 ? 2.75 * e : e;
-  };
-  double lane_load[3] = {nbig > 0 ? acc_cost(big[0]) : 0.0, 0.0, 0.0};  // [0] sT, [1] sA, [2] stream5
-  for (int q = 1; q < q_first; q++) lane_load[1] += acc_cost(big[q]);
-  bool h_done = !h_late;
-  for (int q = q_first; q < nbig; q++) {
-    if (!h_done && jobs[big[q]].is_h) {
-      if ((s = enqueue_h(jev[33]))) return s;
-      if ((s = sort_h_or(big[q]))) return s;
-      h_done = true;
-    }
-    hipStream_t sq = sA;
-    if (multi_lane) {
-      int l = lane_load[0] < lane_load[1] ? 0 : 1;
-      if (lane_load[2] < lane_load[l]) l = 2;
-      lane_load[l] += acc_cost(big[q]);
-      sq = l == 0 ? sT : l == 1 ? sA : ctx->stream5;
-    }
-    if ((s = acc_job(big[q], sq))) return s;
-    acc_stream[q] = sq;
-  }
-  if (!h_done && (s = enqueue_h(jev[33]))) return s;  // (no large h job: H still runs)
-  if ((s = run_small())) return s;
-  // The host waits below are on events of THIS proof's work (not stream syncs): on a pipelined
-  // batch lane the streams soon hold the next proof's work behind it.
-  // ev[10..13]: small multiexps, sorts, accumulations, H; ev[2+q]: tail q
-  BH_TRY_HIP(hipEventRecord(ctx->ev[10], sT));
-  BH_TRY_HIP(hipEventRecord(ctx->ev[11], sS));
-  BH_TRY_HIP(hipEventRecord(ctx->ev[12], sA));
-  BH_TRY_HIP(hipEventRecord(ctx->ev[13], sH));
-  // pipelined batch lanes: the next proof may enqueue its start-up and accumulations now (they
-  // queue behind these on every stream); this proof's tails go in only after the previous
-  // proof's (a tail stream would otherwise hold them behind the next proof's tails)
-  const auto t_hand = std::chrono::steady_clock::now();
-  if (t_lane.after_accs) t_lane.after_accs();
-  if (t_lane.before_tails) t_lane.before_tails();
-  // The last tail right behind its own accumulation, on that lane (every CU): with three lanes
-  // (round 6) the first accumulation's stream may still be running the G2 tail below, which held
-  // the last tail back 0.9 ms at N = 8 (profiles/r06_n8_rank0_timeline.txt, second trace).
-  if (last_full && nbig > 0 && nsmall == 0) tails[nbig - 1] = multi_lane ? acc_stream[nbig - 1] : sT;
-  // The G2 multiexp's reduction tail (continuation fold + reduction of G2 buckets, each addition
-  // ~3x a G1 one) on the first accumulation's stream, every CU, right behind the G2 accumulation,
-  // rather than on a quarter-CU tail stream: with three accumulation lanes the G1 accumulations end
-  // earlier and at N = 8 that latency-bound tail (2.9 + 1.6 + 0.8 ms on 64 CUs) became the rank's
-  // critical path (profiles/r06_n8_rank0_timeline.txt).  Same-box A/B: the 2^22 bench 53.9-54.0 against 54.3-54.8
-  // ms, bh_prove 57.9-58.2 against 58.4-58.9, rehearsal N = 1 / 2 / 8 at or below the base
-  // (profiles/r06_ab_g2_tail.txt).  (On a pipelined batch lane the streams are shared: tail streams.)
-  // (only where no later accumulation queued on that stream: the tail would wait for it)
-  if (!serial && !ctx->borrowed_streams)
-    for (int q = 0; q + 1 < nbig; q++) {
-      if (!jobs[big[q]].g2 || !acc_stream[q]) continue;
-      bool later = false;
-      for (int r = q + 1; r < nbig; r++) later = later || acc_stream[r] == acc_stream[q];
-      if (!later) tails[q] = acc_stream[q];
-    }
-  for (int q = 0; q < nbig; q++) {
-    if ((s = tail_job(big[q], tails[q]))) return s;
-    BH_TRY_HIP(hipEventRecord(ctx->ev[2 + q], tails[q]));
-  }
-  const auto t_enq = std::chrono::steady_clock::now();
-  if (t_lane.after_tails) t_lane.after_tails();
-  float g1_acc_ms = 0, g2_acc_ms = 0;
-  size_t g1_pairs = 0, g2_pairs = 0, g1_adds = 0, g2_adds = 0;
-  int g1_launches = 0, g2_launches = 0;
-  for (int i = 0; i < 6; i++) res1[i] = jac_identity<Fp>();
-  for (int i = 0; i < 2; i++) res2[i] = jac_identity<bh::Fp2>();
-  // Each multiexp's host combine runs as soon as its own tail stream is done (its window sums
-  // are on the host), while later tails still run: only the last one's stays on the critical
-  // path.  The small multiexps (stream sT) finish first.
-  int order[8], nord = 0;
-  for (int i = 0; i < nsmall; i++) order[nord++] = small[i];
-  for (int q = 0; q < nbig; q++) order[nord++] = big[q];
-  for (int o = 0; o < nord; o++) {
-    const int j = order[o];
-    const Job& J = jobs[j];
-    if (o == 0 || o == nsmall) BH_TRY_HIP(hipEventSynchronize(ctx->ev[10]));
-    if (o >= nsmall) BH_TRY_HIP(hipEventSynchronize(ctx->ev[2 + (o - nsmall)]));
-    float t = 0;
-    if (acc_events_on()) (void)hipEventElapsedTime(&t, jev[2 * j], jev[2 * j + 1]);
-    const size_t pairs = (size_t)((unsigned __int128)J.used * (his[j] - los[j]) / std::max<size_t>(J.n, 1));
-    if (J.g2) {
-      res2[J.out] = combine_g2(ctx->host_out2 + 128 * J.out, shapes[j]);
-      g2_acc_ms += t; g2_launches++; g2_pairs += pairs; g2_adds += ctx->host_counts[j];
-    } else {
-      res1[J.out] = combine_g1(ctx->host_out1 + 128 * J.out, shapes[j]);
-      g1_acc_ms += t; g1_launches++; g1_pairs += pairs; g1_adds += ctx->host_counts[j];
-    }
-  }
-  for (int e = 10; e <= 13; e++) BH_TRY_HIP(hipEventSynchronize(ctx->ev[e]));
+  const ProofSchedule P = proof_schedule(sched_input(R, serial, host_in));
+  EnqueueTimes te;
+  if ((s = run_schedule(R, P, &te))) return s;
+
+  AccTotals acc;
+  if ((s = collect_results(R, P, res1, res2, &acc))) return s;
   if (host_in) {
     hin.th.join();
     if (hin.st) return hin.st;
-    res1[jobs[5].out] = hin.a;
-    res1[jobs[6].out] = hin.b1;
-    res2[jobs[7].out] = hin.b2;
+    res1[R.jobs[5].out] = hin.a;
+    res1[R.jobs[6].out] = hin.b1;
+    res2[R.jobs[7].out] = hin.b2;
   }
-  const auto t_gpu = std::chrono::steady_clock::now();
+  const auto t_gpu = HostClock::now();
 
-  const auto t1 = std::chrono::steady_clock::now();
-  static const bool host_timing = getenv("BH_HOST_TIMING") != nullptr;
-  if (host_timing) {
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-      return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    fprintf(stderr, "compute_msms host: ctx %p start %.3f ms (monotonic), first accumulation enqueued %.3f ms, H %.3f, sorts %.3f, accumulations handed on %.3f, enqueue done %.3f, gpu and combines done %.3f, after %.3f\n",
-            (void*)ctx, std::chrono::duration<double, std::milli>(t0.time_since_epoch()).count(), ms(t0, t_acc0), ms(t0, t_h),
-            ms(t0, t_sorts), ms(t0, t_hand), ms(t0, t_enq), ms(t0, t_gpu), ms(t_gpu, t1));
-  }
-  float h_ms = 0;
-  hipEventElapsedTime(&h_ms, ctx->ev[0], ctx->ev[1]);
-  ctx->last_timings[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-  ctx->last_timings[1] = h_ms;
-  ctx->last_timings[2] = g1_acc_ms;
-  ctx->last_timings[3] = g1_launches;
-  ctx->last_timings[4] = (double)g1_pairs;
-  ctx->last_timings[5] = g2_acc_ms;
-  ctx->last_timings[6] = g2_launches;
-  ctx->last_timings[7] = (double)g2_pairs;
-  ctx->last_timings[8] = (double)g1_adds;
-  ctx->last_timings[9] = (double)g2_adds;
-  ctx->last_timings[10] = n_table;
-  ctx->last_timings[11] = n_large;
-  // [21] / [22]: wall time during which at least one G1 / G2 accumulation ran (the union of the
-  // launches' event intervals): with two accumulation lanes G1 launches overlap, so the summed
-  // launch time ([2]) counts that time twice
-  ctx->last_timings[21] = ctx->last_timings[22] = 0;
-  if (acc_events_on()) {
-    for (int g = 0; g < 2; g++) {
-      std::vector<std::pair<float, float>> iv;
-      for (int q = 0; q < nbig; q++) {
-        const int j = big[q];
-        if (jobs[j].g2 != (g == 1)) continue;
-        float a = 0, b = 0;
-        if (hipEventElapsedTime(&a, jev[32], jev[2 * j]) == hipSuccess &&
-            hipEventElapsedTime(&b, jev[32], jev[2 * j + 1]) == hipSuccess)
-          iv.push_back({a, b});
-      }
-      std::sort(iv.begin(), iv.end());
-      double tot = 0, cs = -1e30, ce = -1e30;
-      for (const auto& x : iv) {
-        if (x.first > ce) { if (ce > cs) tot += ce - cs; cs = x.first; ce = x.second; }
-        else ce = std::max(ce, (double)x.second);
-      }
-      if (ce > cs) tot += ce - cs;
-      ctx->last_timings[21 + g] = tot;
-    }
-  }
-  // bytes of the window tables this proof's multiexps read (each distinct table once): for a
-  // shard, its own slices and h share only, not whatever else the Parameters keep resident
-  size_t tb = 0;
-  for (int j = 0; j < 8; j++) {
-    if (!use_table[j]) continue;
-    bool seen = false;
-    for (int q = 0; q < j; q++) seen |= use_table[q] && jobs[q].srs == jobs[j].srs;
-    if (!seen) tb += jobs[j].srs->win->bytes;
-  }
-  ctx->last_timings[12] = (double)tb;
+  const auto t1 = HostClock::now();
+  print_host_timing(ctx, t0, te, t_gpu, t1);
+  write_stats(R, P, acc, std::chrono::duration<double, std::milli>(t1 - t0).count());
   drain.ok = true;
   return BH_OK;
 }
@@ -1627,11 +1567,8 @@ bh_status run_ranks(const std::vector<bh_ctx*>& ctxs, const std::vector<const bh
       bh_ctx* v = ctxs[k];
       std::lock_guard<std::mutex> vl(v->mu);
       BH_TRY_HIP(hipSetDevice(v->device));
-      ShareGeom geom;
       const bool dist = dist_h_eligible(N, w->log_m) && (size_t)N >= dist_h_min_ranks();
-      if (dist) {
-        geom.N = N; geom.rank = k; geom.L = w->log_m; geom.M = w->m / N; geom.C = geom.M / N;
-      }
+      const ShareGeom geom = share_geom(N, k, w->log_m, w->m);
       std::unique_lock<std::shared_mutex> pwr(const_cast<bh_params*>(ps[k])->mu);
       Job jobs[8];
       bh_status s = plan_shard(v, ps[k], w, (size_t)k, (size_t)N, dist ? &geom : nullptr, nullptr, nullptr, nullptr,
@@ -1692,12 +1629,8 @@ bh_status bh_params_prepare_shard(bh_ctx* ctx, bh_params* params, const bh_witne
   if (!same_device(ctx, params, w)) return BH_ERR_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(ctx->mu);
   BH_TRY_HIP(hipSetDevice(ctx->device));
-  ShareGeom geom;
   const bool dist = distributed_h && dist_h_eligible((int)nshards, w->log_m) && nshards >= dist_h_min_ranks();
-  if (dist) {
-    geom.N = (int)nshards; geom.rank = (int)shard; geom.L = w->log_m;
-    geom.M = w->m / nshards; geom.C = geom.M / nshards;
-  }
+  const ShareGeom geom = share_geom((int)nshards, (int)shard, w->log_m, w->m);
   std::unique_lock<std::shared_mutex> pwr(params->mu);
   Job jobs[8];
   return plan_shard(ctx, params, w, shard, nshards, dist ? &geom : nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -1718,7 +1651,7 @@ bh_status bh_prove_witness(bh_ctx* ctx, const bh_params* params, const bh_witnes
   const auto t0 = std::chrono::steady_clock::now();
   assemble_finish(pre.get(), r1, r2, proof_out);
   const double asm_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  ctx->last_timings[0] += asm_ms;
+  ctx->last_timings[STAT_WALL_MS] += asm_ms;
   if (getenv("BH_HOST_TIMING")) fprintf(stderr, "assemble %.3f ms\n", asm_ms);
   return BH_OK;
 }
@@ -2051,7 +1984,7 @@ bh_status bh_prove(bh_ctx* ctx, const bh_params* params, const uint64_t* a, cons
       const size_t m = w->m, nc = w->num_constraints;
       uint32_t* abc = ctx->staging.as<uint32_t>();
       BH_TRY_HIP(hipStreamWaitEvent(sH, up.vec[v], 0));
-      if (v == 0) BH_TRY_HIP(hipEventRecord(ctx->ev[0], sH));
+      if (v == 0) BH_TRY_HIP(hipEventRecord(ctx->ev[EV_H_BEGIN], sH));
       // the ifft's first pass reads the uploaded bls12_381-Montgomery words in place (their radix
       // folded into its scale, run_h_vector); only the padding is written first.  (A conversion
       // kernel first, round 5's first scheme, waited for slots beside the accumulations: 9.5 ms
@@ -2063,7 +1996,7 @@ bh_status bh_prove(bh_ctx* ctx, const bh_params* params, const uint64_t* a, cons
       if (v == 2) {
         // the last pass writes h as canonical scalars, natural order, truncated to m-1 (prover.rs:227-231)
         if ((hs = run_h_final(ctx, D, abc, sH, ctx->hbuf.as<uint32_t>()))) return hs;
-        BH_TRY_HIP(hipEventRecord(ctx->ev[1], sH));
+        BH_TRY_HIP(hipEventRecord(ctx->ev[EV_H_END], sH));
       }
       return BH_OK;
     };
@@ -2090,13 +2023,13 @@ bh_status bh_prove(bh_ctx* ctx, const bh_params* params, const uint64_t* a, cons
   // compute_msms, the H block's end ([12] stays the table bytes)
   {
     float t = 0;
-    ctx->last_timings[13] = hipEventElapsedTime(&t, up.t0, up.ev[0]) == hipSuccess ? t : -1;
+    ctx->last_timings[STAT_UP_AUX_MS] = hipEventElapsedTime(&t, up.t0, up.ev[0]) == hipSuccess ? t : -1;
     for (int v = 0; v < 3; v++)
-      ctx->last_timings[14 + v] = hipEventElapsedTime(&t, up.t0, up.vec[v]) == hipSuccess ? t : -1;
-    ctx->last_timings[17] = hipEventElapsedTime(&t, up.t0, ctx->ev[1]) == hipSuccess ? t : -1;
+      ctx->last_timings[STAT_UP_VEC_MS + v] = hipEventElapsedTime(&t, up.t0, up.vec[v]) == hipSuccess ? t : -1;
+    ctx->last_timings[STAT_UP_H_END_MS] = hipEventElapsedTime(&t, up.t0, ctx->ev[EV_H_END]) == hipSuccess ? t : -1;
   }
   assemble_finish(pre.get(), r1, r2, proof_out);
-  ctx->last_timings[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  ctx->last_timings[STAT_WALL_MS] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return BH_OK;
 }
 
@@ -2114,3 +2047,36 @@ bh_status bh_last_stats(const bh_ctx* ctx, double* out, size_t n) {
 }
 
 }  // extern "C"
+
+// proof_schedule() on flat arrays, for the host test (tests/test_proof_schedule_cpu.py; not part of
+// the public header).  jobs: 8 x (len, used, W, is_h, g2); rel: 8 x 8 SchedRel, [i][j] = what j's
+// sort can take from i's; flags: bit 0 serial, 1 borrowed_streams, 2 cu_masked, 3 host_in,
+// 4 uploading, 5 distributed.  out: nbig, big[8], nsmall, small[8], h_first, first_own, multi_lane,
+// wait_j, nsteps, then per step op, job, stream, kind, src, pre, wait_h, wait_sorted, slot.
+// Returns the words written, -1 if cap is too small.
+extern "C" int bh_selftest_proof_schedule(const uint64_t* jobs, const uint8_t* rel, unsigned flags, int64_t* out,
+                                          size_t cap) {
+  if (!jobs || !rel || !out) return -1;
+  SchedIn in;
+  for (int j = 0; j < 8; j++) {
+    const uint64_t* q = jobs + 5 * j;
+    in.job[j] = SchedJob{(size_t)q[0], (size_t)q[1], (int)q[2], q[3] != 0, q[4] != 0};
+    for (int i = 0; i < 8; i++) in.rel[i][j] = rel[8 * i + j];
+  }
+  in.serial = flags & 1; in.borrowed_streams = flags & 2; in.cu_masked = flags & 4;
+  in.host_in = flags & 8; in.uploading = flags & 16; in.distributed = flags & 32;
+  const ProofSchedule P = proof_schedule(in);
+  if (cap < 23 + 9 * (size_t)P.nsteps) return -1;
+  size_t k = 0;
+  out[k++] = P.nbig;
+  for (int q = 0; q < 8; q++) out[k++] = q < P.nbig ? P.big[q] : -1;
+  out[k++] = P.nsmall;
+  for (int q = 0; q < 8; q++) out[k++] = q < P.nsmall ? P.small[q] : -1;
+  out[k++] = P.h_first; out[k++] = P.first_own; out[k++] = P.multi_lane; out[k++] = P.wait_j; out[k++] = P.nsteps;
+  for (int i = 0; i < P.nsteps; i++) {
+    const SchedStep& t = P.steps[i];
+    const int8_t f[9] = {t.op, t.job, t.stream, t.kind, t.src, t.pre, t.wait_h, t.wait_sorted, t.slot};
+    for (int8_t v : f) out[k++] = v;
+  }
+  return (int)k;
+}
