@@ -186,6 +186,9 @@ extern "C" void* scalar_pool_take(int device, size_t bytes, size_t* got);
 // selftest.hip (tests/test_gpu_selftest.py): fe2_mul_sub_kara and the two-product form on
 // caller-chosen operands
 extern "C" bh_status bh_selftest_fp2_mul_sub(int device, const uint32_t* in, size_t n, uint32_t* out);
+// selftest.hip (tests/test_gpu_field_products.py): every product form of field.cuh in both
+// column forms on caller-chosen operands
+extern "C" bh_status bh_selftest_field_products(int device, const uint32_t* in, size_t n, uint32_t* out);
 // prover.hip (tests/test_proof_schedule_cpu.py): proof_schedule() of proof_schedule.h on flat arrays
 extern "C" int bh_selftest_proof_schedule(const uint64_t* jobs, const uint8_t* rel, unsigned flags, int64_t* out,
                                           size_t cap);

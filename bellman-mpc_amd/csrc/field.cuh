@@ -61,63 +61,97 @@ BH_DEV Fe<C> fe_one() {  // Montgomery form of 1
   return r;
 }
 
-// One step of a column chain: acc + a*b as ONE v_mad_u64_u32 with acc as its addend.  Written as
-// plain C (acc += (uint64_t)a * b) the compiler's reassociation starts every column on a fresh
-// chain of products and adds the carried accumulator afterwards (one 64-bit add per column); as
-// an opaque instruction the column stays one chain seeded with the carry (the hazard recogniser
-// follows each with an s_nop 0, which is not VALU work, and the chain is latency-bound per wave).
-// Measured (profiles/r06_ab_mul_chain.txt): Fr (the NTT, 4 waves per SIMD) -16 VALU per butterfly,
-// 2^22 proof -0.2 ms; Fp (the accumulations, 2 waves per SIMD) 5 129 -> 4 745 VALU per G1 madd but
-// the proof +1.2 ms and N = 8 +1.2 ms -- the latency costs more than the merges.  So Fr only.
-template <class C>
-struct MulChain {
-  static constexpr bool value = C::N == 9;  // FrCfg
-};
+// ---------------------------------------------------------------- column chains
+// One step of a column: acc += a*b, one v_mad_u64_u32.  Written as plain C alone, the compiler's
+// reassociation (which rewrites add trees whose inner nodes have a single use) starts every
+// column on a fresh chain of products and adds the carried accumulator afterwards: one 64-bit
+// merge add per column (28 per Fp product).  With CH, every partial sum gets a second use that
+// vanishes before code generation -- an assumption that it differs from a word of
+// bh_column_fence -- so the tree is left as written: each column is ONE chain whose first mad
+// takes the shifted carry as its addend.  The fence emits nothing (no compare, no load, no
+// s_nop; the 8 KiB table stays in the code object, unread).
+//
+// Soundness: every word of bh_column_fence holds 2^64 - 1 and is never written (nothing in the
+// library takes its address or copies to it; a __device__ variable may be initialised from the
+// host, so the optimiser cannot fold the load and cannot decide the comparison from the partial
+// sum's known bits -- which is what erodes a fence against a constant once operands come from
+// masked limbs: 184 of a G1 mixed addition's 262 merges came back).  Each fence of a product
+// reads its own word (`site`, a constant after unrolling): with one shared word every
+// assumption of a kernel hangs on the same value and the optimiser's per-value assumption
+// scans go quadratic (a schoolbook-Fp2 mixed addition compiled in 243 s instead of 23 s; 5 s
+// without fences).
+// No accumulator reaches 2^64 - 1: the worst column of every product form below, at the limb
+// and operand maxima stated with it, is computed in tests/test_field_column_bounds_cpu.py
+// (largest: fe2_mul_sub_kara's biased sums < 61.1 * 2^58; fe_mul2 < 2^63.4; fe_mul < 2^62.9).
+// The signed accumulator of fe2_mul_kara lies in (-2^62, 2^63 - 2^60); it is fenced with its sign
+// bit flipped (col_fence_signed), i.e. against 2^63 - 1.
+//
+// BH_COLUMN_CHAIN (default 1) chooses the form for the translation unit that includes this
+// header, as BH_FP2_KARATSUBA does for Fp2 products; both forms give identical limbs (only the
+// association order of exact 64-bit sums differs; tests/test_gpu_field_products.py compares
+// them side by side).  An earlier form made each mad an opaque inline-asm statement: the compiler
+// follows every asm statement with an s_nop 0, one issue slot per mad, and that form's +1.2 ms on
+// the 2^22 proof (profiles/r06_ab_mul_chain.txt) was this cost, not chain latency.
+#ifndef BH_COLUMN_CHAIN
+#define BH_COLUMN_CHAIN 1
+#endif
+constexpr bool BH_CHAIN = BH_COLUMN_CHAIN != 0;
+
+constexpr int BH_FENCE_SITES = 1024;
+struct BhColumnFence { uint64_t v[BH_FENCE_SITES]; };
+constexpr BhColumnFence bh_column_fence_init() {
+  BhColumnFence f{};
+  for (int i = 0; i < BH_FENCE_SITES; i++) f.v[i] = ~0ull;
+  return f;
+}
+inline __device__ BhColumnFence bh_column_fence = bh_column_fence_init();
+
+BH_DEV void col_fence(uint64_t acc, int& site) {
+  __builtin_assume(acc != bh_column_fence.v[site & (BH_FENCE_SITES - 1)]);
+  site++;
+}
+BH_DEV void col_fence_signed(int64_t acc, int& site) { col_fence((uint64_t)acc ^ (1ull << 63), site); }
+
 template <bool CH>
-BH_DEV void mac(uint64_t& acc, uint32_t a, uint32_t b) {
-  if (CH) {
-    uint64_t r, sc;
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(sc) : "v"(a), "v"(b), "v"(acc));
-    acc = r;
-  } else {
-    acc += (uint64_t)a * b;
-  }
+BH_DEV void mac(uint64_t& acc, uint32_t a, uint32_t b, int& site) {
+  acc += (uint64_t)a * b;
+  if (CH) col_fence(acc, site);
 }
 // ... times a modulus limb (a compile-time constant: an SGPR operand)
 template <bool CH>
-BH_DEV void mac_p(uint64_t& acc, uint32_t m, uint32_t p) {
-  if (CH) {
-    uint64_t r, sc;
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(sc) : "v"(m), "s"(p), "v"(acc));
-    acc = r;
-  } else {
-    acc += (uint64_t)m * p;
-  }
+BH_DEV void mac_p(uint64_t& acc, uint32_t m, uint32_t p, int& site) {
+  acc += (uint64_t)m * p;
+  if (CH) col_fence(acc, site);
+}
+template <bool CH>
+BH_DEV void mac_p(int64_t& acc, uint32_t m, uint32_t p, int& site) {
+  acc += (int64_t)((uint64_t)m * p);
+  if (CH) col_fence_signed(acc, site);
 }
 
 // Montgomery product, FIPS column order. Output < 2p (see header).
 // A modulus with p = 1 (mod 2^BITS) (Fr) has m_k = -acc mod 2^BITS, so acc + m_k * p_0 is acc
 // rounded up to a multiple of 2^BITS: (acc + MASK) >> BITS, no product and no 64-bit m_k.
-// DFp keeps two independent chains (a*b and m*p) per column, which the compiler schedules for
-// latency; Fr runs each column as one carry-seeded chain of opaque mads (MulChain, above).
-template <class C>
+// CH: each column one carry-seeded chain (above).  Without it DFp keeps two independent chains
+// (a*b and m*p) per column and merges them, and Fr is left to the compiler's association.
+template <class C, bool CH = BH_CHAIN>
 BH_DEV Fe<C> fe_mul(const Fe<C>& a, const Fe<C>& b) {
   constexpr int N = C::N;
   constexpr bool P0_ONE = C::P[0] == 1u;
-  constexpr bool CH = MulChain<C>::value;
   constexpr bool TWO_CHAINS = N > 9 && !CH;
   Fe<C> r;
   uint32_t m[N];
+  int site = 0;  // numbers the fences of this product (col_fence)
   uint64_t acc = 0;
 #pragma unroll
   for (int k = 0; k < 2 * N - 1; k++) {
     uint64_t acc2 = 0;
 #pragma unroll
-    for (int i = (k < N ? 0 : k - N + 1); i <= (k < N ? k : N - 1); i++) mac<CH>(acc, a.v[i], b.v[k - i]);
+    for (int i = (k < N ? 0 : k - N + 1); i <= (k < N ? k : N - 1); i++) mac<CH>(acc, a.v[i], b.v[k - i], site);
 #pragma unroll
     for (int i = (k < N ? 0 : k - N + 1); i < (k < N ? k : N); i++) {
       if (TWO_CHAINS) acc2 += (uint64_t)m[i] * C::P[k - i];
-      else mac_p<CH>(acc, m[i], C::P[k - i]);
+      else mac_p<CH>(acc, m[i], C::P[k - i], site);
     }
     if (TWO_CHAINS) acc += acc2;
     if (k < N) {
@@ -126,7 +160,7 @@ BH_DEV Fe<C> fe_mul(const Fe<C>& a, const Fe<C>& b) {
         acc = (acc + C::MASK) >> C::BITS;
         continue;
       }
-      mac_p<CH>(acc, m[k], C::P[0]);
+      mac_p<CH>(acc, m[k], C::P[0], site);
     } else {
       r.v[k - N] = (uint32_t)acc & C::MASK;
     }
@@ -137,26 +171,26 @@ BH_DEV Fe<C> fe_mul(const Fe<C>& a, const Fe<C>& b) {
 }
 
 // x * R^-1 (fe_mul(x, 1) without the zero products): out of Montgomery form, <= p for x < R
-template <class C>
+template <class C, bool CH = BH_CHAIN>
 BH_DEV Fe<C> fe_from_mont(const Fe<C>& a) {
   constexpr int N = C::N;
-  constexpr bool CH = MulChain<C>::value;
   constexpr bool P0_ONE = C::P[0] == 1u;
   Fe<C> r;
   uint32_t m[N];
+  int site = 0;  // numbers the fences of this product (col_fence)
   uint64_t acc = 0;
 #pragma unroll
   for (int k = 0; k < 2 * N - 1; k++) {
     if (k < N) acc += a.v[k];
 #pragma unroll
-    for (int i = (k < N ? 0 : k - N + 1); i < (k < N ? k : N); i++) mac_p<CH>(acc, m[i], C::P[k - i]);
+    for (int i = (k < N ? 0 : k - N + 1); i < (k < N ? k : N); i++) mac_p<CH>(acc, m[i], C::P[k - i], site);
     if (k < N) {
       m[k] = ((uint32_t)acc * C::INV) & C::MASK;
       if (P0_ONE) {  // as in fe_mul
         acc = (acc + C::MASK) >> C::BITS;
         continue;
       }
-      mac_p<CH>(acc, m[k], C::P[0]);
+      mac_p<CH>(acc, m[k], C::P[0], site);
     } else {
       r.v[k - N] = (uint32_t)acc & C::MASK;
     }
@@ -170,26 +204,26 @@ BH_DEV Fe<C> fe_from_mont(const Fe<C>& a) {
 // products of both pairs and the m*p terms -- at most 3N = 42 products < 2^58 each for DFp,
 // so the 64-bit accumulator still needs no carry handling (2^63.4).  Output < 2p when the
 // operand bounds (in multiples of p) satisfy A*B + C*D < R/p (2^25 for DFp).
-template <class C>
+template <class C, bool CH = BH_CHAIN>
 BH_DEV Fe<C> fe_mul2(const Fe<C>& a, const Fe<C>& b, const Fe<C>& c, const Fe<C>& d) {
   constexpr int N = C::N;
   static_assert(3 * N < 64, "3N products < 2^58 plus the carry must fit the 64-bit column accumulator");
-  constexpr bool CH = MulChain<C>::value;
   Fe<C> r;
   uint32_t m[N];
+  int site = 0;  // numbers the fences of this product (col_fence)
   uint64_t acc = 0;
 #pragma unroll
   for (int k = 0; k < 2 * N - 1; k++) {
 #pragma unroll
     for (int i = (k < N ? 0 : k - N + 1); i <= (k < N ? k : N - 1); i++) {
-      mac<CH>(acc, a.v[i], b.v[k - i]);
-      mac<CH>(acc, c.v[i], d.v[k - i]);
+      mac<CH>(acc, a.v[i], b.v[k - i], site);
+      mac<CH>(acc, c.v[i], d.v[k - i], site);
     }
 #pragma unroll
-    for (int i = (k < N ? 0 : k - N + 1); i < (k < N ? k : N); i++) mac_p<CH>(acc, m[i], C::P[k - i]);
+    for (int i = (k < N ? 0 : k - N + 1); i < (k < N ? k : N); i++) mac_p<CH>(acc, m[i], C::P[k - i], site);
     if (k < N) {
       m[k] = ((uint32_t)acc * C::INV) & C::MASK;
-      mac_p<CH>(acc, m[k], C::P[0]);
+      mac_p<CH>(acc, m[k], C::P[0], site);
     } else {
       r.v[k - N] = (uint32_t)acc & C::MASK;
     }
@@ -200,14 +234,14 @@ BH_DEV Fe<C> fe_mul2(const Fe<C>& a, const Fe<C>& b, const Fe<C>& c, const Fe<C>
 }
 
 // Montgomery square: cross products computed once against 2*a (limbs < 2^30).
-template <class C>
+template <class C, bool CH = BH_CHAIN>
 BH_DEV Fe<C> fe_sqr(const Fe<C>& a) {
   constexpr int N = C::N;
   Fe<C> r;
-  constexpr bool CH = MulChain<C>::value;
   uint32_t m[N], a2[N];
 #pragma unroll
   for (int i = 0; i < N; i++) a2[i] = a.v[i] << 1;
+  int site = 0;  // numbers the fences of this product (col_fence)
   uint64_t acc = 0;
 #pragma unroll
   for (int k = 0; k < 2 * N - 1; k++) {
@@ -216,14 +250,14 @@ BH_DEV Fe<C> fe_sqr(const Fe<C>& a) {
 #pragma unroll
     for (int i = lo; i <= hi; i++) {
       const int j = k - i;
-      if (i < j) mac<CH>(acc, a.v[i], a2[j]);
-      else if (i == j) mac<CH>(acc, a.v[i], a.v[i]);
+      if (i < j) mac<CH>(acc, a.v[i], a2[j], site);
+      else if (i == j) mac<CH>(acc, a.v[i], a.v[i], site);
     }
 #pragma unroll
-    for (int i = (k < N ? 0 : k - N + 1); i < (k < N ? k : N); i++) mac_p<CH>(acc, m[i], C::P[k - i]);
+    for (int i = (k < N ? 0 : k - N + 1); i < (k < N ? k : N); i++) mac_p<CH>(acc, m[i], C::P[k - i], site);
     if (k < N) {
       m[k] = ((uint32_t)acc * C::INV) & C::MASK;
-      mac_p<CH>(acc, m[k], C::P[0]);
+      mac_p<CH>(acc, m[k], C::P[0], site);
     } else {
       r.v[k - N] = (uint32_t)acc & C::MASK;
     }
@@ -416,7 +450,7 @@ using FpOps = FpOpsT<FpCfg>;  // 14 x 29-bit limbs
 // accumulator; both halves get their own interleaved Montgomery reduction.  c0 = (X + M p)/R
 // with X > -(128p)^2 lies in (-p/2^11, 2p): one conditional +p makes it >= 0.  Inputs < 128p
 // with 29-bit limbs (so a0+a1 limbs < 2^30, products < 2^60, 14-term columns < 2^63.9).
-template <class C>
+template <class C, bool CH = BH_CHAIN>
 BH_DEV void fe2_mul_kara(const Fe<C>& a0, const Fe<C>& a1, const Fe<C>& b0, const Fe<C>& b1, Fe<C>& r0,
                          Fe<C>& r1) {
   constexpr int N = C::N;
@@ -426,6 +460,7 @@ BH_DEV void fe2_mul_kara(const Fe<C>& a0, const Fe<C>& a1, const Fe<C>& b0, cons
     sa[i] = a0.v[i] + a1.v[i];
     sb[i] = b0.v[i] + b1.v[i];
   }
+  int site = 0;  // numbers the fences of this product (col_fence)
   int64_t acc0 = 0;
   uint64_t acc1 = 0;
 #pragma unroll
@@ -437,18 +472,23 @@ BH_DEV void fe2_mul_kara(const Fe<C>& a0, const Fe<C>& a1, const Fe<C>& b0, cons
       t1 += (uint64_t)a1.v[i] * b1.v[k - i];
       t2 += (uint64_t)sa[i] * sb[k - i];
     }
+    // (with CH the m*p mads below continue from these sums: one chain per half, seeded here)
     acc0 += (int64_t)(t0 - t1);
     acc1 += t2 - t0 - t1;
+    if (CH) {
+      col_fence_signed(acc0, site);
+      col_fence(acc1, site);
+    }
 #pragma unroll
     for (int i = (k < N ? 0 : k - N + 1); i < (k < N ? k : N); i++) {
-      acc0 += (int64_t)((uint64_t)m0[i] * C::P[k - i]);
-      acc1 += (uint64_t)m1[i] * C::P[k - i];
+      mac_p<CH>(acc0, m0[i], C::P[k - i], site);
+      mac_p<CH>(acc1, m1[i], C::P[k - i], site);
     }
     if (k < N) {
       m0[k] = ((uint32_t)acc0 * C::INV) & C::MASK;
-      acc0 += (int64_t)((uint64_t)m0[k] * C::P[0]);
+      mac_p<CH>(acc0, m0[k], C::P[0], site);
       m1[k] = ((uint32_t)acc1 * C::INV) & C::MASK;
-      acc1 += (uint64_t)m1[k] * C::P[0];
+      mac_p<CH>(acc1, m1[k], C::P[0], site);
     } else {
       r0.v[k - N] = (uint32_t)acc0 & C::MASK;
       r1.v[k - N] = (uint32_t)acc1 & C::MASK;
@@ -482,7 +522,7 @@ BH_DEV void fe2_mul_kara(const Fe<C>& a0, const Fe<C>& a1, const Fe<C>& b0, cons
 // (acc >> 29) - (BIAS >> 29), i.e. the next column starts from (acc >> 29) + (BIAS - (BIAS >> 29)).
 // The result (X + M p) / R lies in (-p, 2p) for |X| < 2^25 p^2 (R = 2^406 > 2^25 p): a negative
 // half gets + p, leaving [0, 2p).
-template <class C>
+template <class C, bool CH = BH_CHAIN>
 BH_DEV void fe2_mul_sub_kara(const Fe<C>& a0, const Fe<C>& a1, const Fe<C>& b0, const Fe<C>& b1, const Fe<C>& c0,
                              const Fe<C>& c1, const Fe<C>& d0, const Fe<C>& d1, Fe<C>& r0, Fe<C>& r1) {
   constexpr int N = C::N;
@@ -496,6 +536,7 @@ BH_DEV void fe2_mul_sub_kara(const Fe<C>& a0, const Fe<C>& a1, const Fe<C>& b0, 
     sc[i] = c0.v[i] + c1.v[i];
     sd[i] = d0.v[i] + d1.v[i];
   }
+  int site = 0;  // numbers the fences of this product (col_fence)
   uint64_t acc0 = BIAS, acc1 = BIAS;
 #pragma unroll
   for (int k = 0; k < 2 * N - 1; k++) {
@@ -512,16 +553,20 @@ BH_DEV void fe2_mul_sub_kara(const Fe<C>& a0, const Fe<C>& a1, const Fe<C>& b0, 
     // (two's complement: the differences are exact mod 2^64 and the biased sums are in range)
     acc0 += (t0 - t1) - (u0 - u1);
     acc1 += (t2 - t0 - t1) - (u2 - u0 - u1);
+    if (CH) {
+      col_fence(acc0, site);
+      col_fence(acc1, site);
+    }
 #pragma unroll
     for (int i = (k < N ? 0 : k - N + 1); i < (k < N ? k : N); i++) {
-      acc0 += (uint64_t)m0[i] * C::P[k - i];
-      acc1 += (uint64_t)m1[i] * C::P[k - i];
+      mac_p<CH>(acc0, m0[i], C::P[k - i], site);
+      mac_p<CH>(acc1, m1[i], C::P[k - i], site);
     }
     if (k < N) {
       m0[k] = ((uint32_t)acc0 * C::INV) & C::MASK;
-      acc0 += (uint64_t)m0[k] * C::P[0];
+      mac_p<CH>(acc0, m0[k], C::P[0], site);
       m1[k] = ((uint32_t)acc1 * C::INV) & C::MASK;
-      acc1 += (uint64_t)m1[k] * C::P[0];
+      mac_p<CH>(acc1, m1[k], C::P[0], site);
     } else {
       r0.v[k - N] = (uint32_t)acc0 & C::MASK;
       r1.v[k - N] = (uint32_t)acc1 & C::MASK;
