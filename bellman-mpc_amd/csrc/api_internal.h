@@ -189,6 +189,27 @@ extern "C" bh_status bh_selftest_fp2_mul_sub(int device, const uint32_t* in, siz
 // selftest.hip (tests/test_gpu_field_products.py): every product form of field.cuh in both
 // column forms on caller-chosen operands
 extern "C" bh_status bh_selftest_field_products(int device, const uint32_t* in, size_t n, uint32_t* out);
+// selftest.hip (tests/test_gpu_field_misc.py): fe_is_zero, fe_reduce_full, fe_csub, neg_canonical,
+// fe_sub<K>, fe_add and pack/unpack (Fp, and Fr where the library instantiates them)
+extern "C" bh_status bh_selftest_field_misc(int device, const uint32_t* in, size_t n, uint32_t* out);
+// selftest_group.hip (tests/test_gpu_group_law.py): one CurveOps operation on caller-chosen raw
+// limbs; unit 0: G1, 1: G2 in the default field form, 2: G2 in msm_g2_acc.hip's form;
+// op 0: madd, 1: madd of neg_affine(base), 2: add, 3: dbl, 4: dbl_affine, 5: reduce;
+// unit_info[0] = the unit's BH_COLUMN_CHAIN, [1] = whether it defines BH_FP2_KARATSUBA
+extern "C" bh_status bh_selftest_group_law(int device, int unit, int op, const uint32_t* in, size_t n, uint32_t* out,
+                                           uint32_t* unit_info);
+namespace bh {
+bh_status selftest_group_law_kara(int device, int op, const uint32_t* in, size_t n, uint32_t* out,
+                                  uint32_t* unit_info);
+}
+// selftest.hip (tests/test_gpu_accumulate.py): one launch of an accumulation kernel on a
+// caller-ordered, host-validated entry list (group 0: G1, 1: G2; kernel 0: k_accumulate_pf,
+// 1: k_accumulate_g2d; msm_selftest_accumulate in msm_impl.cuh)
+extern "C" bh_status bh_selftest_accumulate(int device, int group, int kernel, const uint32_t* bases, size_t nbases,
+                                            uint32_t rec, const uint32_t* entries, size_t n_entries,
+                                            const uint32_t* offsets, size_t nbt, uint32_t S, uint32_t b_lo,
+                                            uint32_t b_hi, uint32_t* bucket_sums, uint32_t* conts,
+                                            uint32_t* cont_bucket);
 // prover.hip (tests/test_proof_schedule_cpu.py): proof_schedule() of proof_schedule.h on flat arrays
 extern "C" int bh_selftest_proof_schedule(const uint64_t* jobs, const uint8_t* rel, unsigned flags, int64_t* out,
                                           size_t cap);

@@ -10,6 +10,8 @@
 // Bounds (multiples of p, see field.cuh): with MB = product bound of the field,
 //   X < XB = MB + K1,  Y < YB = MB + K3,  ZZ, ZZZ < MB
 // and every subtraction constant K is chosen >= the subtrahend's bound.
+// tests/test_gpu_group_law.py (bh_selftest_group_law, selftest_group.cuh) pins these bounds: every
+// operation on inputs at each multiple of p the bounds allow, the output bounds asserted.
 #pragma once
 #include "field.cuh"
 

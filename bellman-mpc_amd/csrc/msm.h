@@ -119,6 +119,16 @@ hipError_t msm_sort(MsmWorkspace<C>& ws, hipStream_t st, const uint32_t* d_scala
 template <class C>
 hipError_t msm_accumulate(MsmWorkspace<C>& ws, hipStream_t st, const uint32_t* d_bases, size_t n, const MsmShape& sh,
                           MsmTiming* timing);
+// One launch of an accumulation kernel (kernel 0: k_accumulate_pf<C>, 1: k_accumulate_g2d<C>, G2
+// only) on host arrays the caller has validated (bh_selftest_accumulate, selftest.hip): uploads
+// bases, entries and offsets[nbt + 1], fills bucket_sums[nbt], conts[segs] and cont_bucket[segs]
+// (segs = ceil(E / S)) with 0xFF bytes, launches with 256 threads per block as msm_accumulate does,
+// and copies the three arrays back.
+template <class C>
+hipError_t msm_selftest_accumulate(int kernel, const uint32_t* h_bases, size_t nbases, uint32_t rec,
+                                   const uint32_t* h_entries, size_t E, const uint32_t* h_offsets, size_t nbt,
+                                   uint32_t S, uint32_t b_lo, uint32_t b_hi, uint32_t* h_bucket_sums, uint32_t* h_conts,
+                                   uint32_t* h_cont_bucket);
 template <class C>
 hipError_t msm_front(MsmWorkspace<C>& ws, hipStream_t st, const uint32_t* d_bases, const uint32_t* d_scalars,
                      size_t n, const int32_t* d_idx, uint32_t base_offset, const MsmShape& sh, MsmTiming* timing);

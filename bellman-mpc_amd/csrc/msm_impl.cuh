@@ -957,6 +957,49 @@ hipError_t msm_accumulate(MsmWorkspace<C>& ws, hipStream_t st, const uint32_t* d
   return hipGetLastError();
 }
 
+// The accumulation kernels on an entry list in the caller's order (msm.h; the arguments are
+// validated by bh_selftest_accumulate: the kernels index memory from these arrays).
+template <class C>
+hipError_t msm_selftest_accumulate(int kernel, const uint32_t* h_bases, size_t nbases, uint32_t rec,
+                                   const uint32_t* h_entries, size_t E, const uint32_t* h_offsets, size_t nbt,
+                                   uint32_t S, uint32_t b_lo, uint32_t b_hi, uint32_t* h_bucket_sums, uint32_t* h_conts,
+                                   uint32_t* h_cont_bucket) {
+  using Pt = typename C::P;
+  const size_t segs = (E + S - 1) / S;
+  struct Buf {
+    void* p = nullptr;
+    ~Buf() { if (p) (void)hipFree(p); }
+  } bases, entries, offsets, sums, conts, cb;
+  hipError_t e;
+  auto up = [&](Buf& b, const void* src, size_t bytes) {
+    if ((e = hipMalloc(&b.p, bytes)) != hipSuccess) return e;
+    return e = hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
+  };
+  auto filled = [&](Buf& b, size_t bytes) {
+    if ((e = hipMalloc(&b.p, bytes)) != hipSuccess) return e;
+    return e = hipMemset(b.p, 0xff, bytes);
+  };
+  if (up(bases, h_bases, nbases * rec * 4) != hipSuccess || up(entries, h_entries, E * 4) != hipSuccess ||
+      up(offsets, h_offsets, (nbt + 1) * 4) != hipSuccess || filled(sums, nbt * sizeof(Pt)) != hipSuccess ||
+      filled(conts, segs * sizeof(Pt)) != hipSuccess || filled(cb, segs * 4) != hipSuccess)
+    return e;
+  const dim3 grid(msm_blocks_for(segs, 256)), block(256);
+  if constexpr (!std::is_same<C, G1Ops>::value) {
+    if (kernel == 1)
+      hipLaunchKernelGGL(k_accumulate_g2d<C>, grid, block, 0, nullptr, (const uint32_t*)entries.p,
+                         (const uint32_t*)offsets.p, (uint32_t)nbt, (const uint32_t*)bases.p, rec, S, b_lo, b_hi,
+                         (Pt*)sums.p, (Pt*)conts.p, (uint32_t*)cb.p);
+  }
+  if (kernel == 0)
+    hipLaunchKernelGGL(k_accumulate_pf<C>, grid, block, 0, nullptr, (const uint32_t*)entries.p,
+                       (const uint32_t*)offsets.p, (uint32_t)nbt, (const uint32_t*)bases.p, rec, S, b_lo, b_hi,
+                       (Pt*)sums.p, (Pt*)conts.p, (uint32_t*)cb.p);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = hipMemcpy(h_bucket_sums, sums.p, nbt * sizeof(Pt), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+  if ((e = hipMemcpy(h_conts, conts.p, segs * sizeof(Pt), hipMemcpyDeviceToHost)) != hipSuccess) return e;
+  return hipMemcpy(h_cont_bucket, cb.p, segs * 4, hipMemcpyDeviceToHost);
+}
+
 // Front half of one multiexp: sort + accumulation, stream-ordered on st.
 template <class C>
 hipError_t msm_front(MsmWorkspace<C>& ws, hipStream_t st, const uint32_t* d_bases, const uint32_t* d_scalars,

@@ -118,11 +118,12 @@ def test_msm_identity_base_semantics(ctx, golden):
 
 @pytest.mark.parametrize("g2", [False, True])
 def test_msm_exceptional_additions_in_one_bucket(ctx, g2):
-    """Equal and opposite bases under equal exponents land next to each other in one bucket per
-    window, so the accumulation meets acc == base (a doubling) and acc == -base (the identity), and
-    the reductions add equal partial sums: the cases curve.cuh folds into the addition's own
-    instruction stream (G1 madd, both groups' full addition).  Compared with the oracle's multiexp
-    (multiexp.rs:159-281)."""
+    """Equal and opposite bases under equal exponents land in one bucket per window.  Their order
+    inside the bucket is decided by the sort's LDS atomics, not by this test, so which doublings
+    and identities the accumulation meets is not chosen here (test_gpu_accumulate.py drives the
+    accumulation kernels on an ordered entry list for that); the reductions add equal partial
+    sums, the case curve.cuh folds into the full addition's own instruction stream.  Compared
+    with the oracle's multiexp (multiexp.rs:159-281)."""
     bh = _bh()
     from oracle import bellman as bm
     from oracle import bls12_381 as bls
