@@ -210,6 +210,24 @@ extern "C" bh_status bh_selftest_accumulate(int device, int group, int kernel, c
                                             const uint32_t* offsets, size_t nbt, uint32_t S, uint32_t b_lo,
                                             uint32_t b_hi, uint32_t* bucket_sums, uint32_t* conts,
                                             uint32_t* cont_bucket);
+// selftest.hip (tests/test_gpu_digit_sort.py): the layer of msm_common.hip between a caller's
+// scalars and the accumulation kernels, through the host functions of msm.h on validated host
+// arrays: sort_entries + max_span, derive_sorted, exclusive_scan and its device-bounded form
+// (dn < 0: unbounded), scalars_prepare, density_index
+extern "C" bh_status bh_selftest_digit_sort(int device, const uint32_t* scalars, size_t n, const int32_t* idx,
+                                            uint32_t base_offset, int c, int pre, uint32_t bk_lo, uint32_t bk_hi,
+                                            uint32_t S, uint32_t* entries, uint32_t* counts, uint32_t* offsets,
+                                            uint32_t* span_words, uint32_t* n_span_words);
+extern "C" bh_status bh_selftest_derive_sorted(int device, const uint32_t* src_entries, size_t Emax,
+                                               const uint32_t* src_offsets, size_t nbt, int pre, uint32_t W,
+                                               uint32_t src_off, const int32_t* idx, size_t n_idx, size_t b0,
+                                               size_t b1, uint32_t* dst_entries, uint32_t* dst_counts,
+                                               uint32_t* dst_offsets);
+extern "C" bh_status bh_selftest_scan(int device, const uint32_t* in, size_t n, int64_t dn, uint32_t* out);
+extern "C" bh_status bh_selftest_scalars_prepare(int device, const uint32_t* in, size_t n, int mode, int log_perm,
+                                                 uint32_t* out);
+extern "C" bh_status bh_selftest_density_index(int device, const uint64_t* words, size_t n, uint32_t base_offset,
+                                               int32_t* idx);
 // prover.hip (tests/test_proof_schedule_cpu.py): proof_schedule() of proof_schedule.h on flat arrays
 extern "C" int bh_selftest_proof_schedule(const uint64_t* jobs, const uint8_t* rel, unsigned flags, int64_t* out,
                                           size_t cap);

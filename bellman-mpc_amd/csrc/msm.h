@@ -166,6 +166,10 @@ inline uint32_t max_span_host(const uint32_t* h_words, size_t nbt) {
 hipError_t max_span(const uint32_t* counts, const uint32_t* offsets, size_t nbt, uint32_t S, uint32_t* d_words,
                     uint32_t* h_words, hipStream_t st);
 void exclusive_scan(const uint32_t* in, uint32_t* out, size_t n, uint32_t* scratch, hipStream_t st);
+// the scan bounded by a device word (only elements 0 .. *dn are read and written), as
+// derive_sorted runs it; declared for bh_selftest_scan
+void exclusive_scan_bounded(const uint32_t* in, uint32_t* out, size_t n, uint32_t* scratch, hipStream_t st,
+                            const uint32_t* dn);
 hipError_t scalars_prepare(const uint32_t* d_in, uint32_t* d_out, size_t n, int mode, int log_perm, hipStream_t st);
 hipError_t density_index(const uint64_t* d_words, size_t n, uint32_t base_offset, int32_t* d_idx, uint32_t* d_tmp,
                          uint32_t* d_scan_scratch, hipStream_t st);

@@ -6,11 +6,15 @@
 // buckets by parts (229-233) and Horner-combines the windows (244-249).
 // Here the same sum is computed as a data-parallel pipeline:
 //
-//   k_hist      one thread per scalar: signed c-bit digits (|d| <= 2^(c-1)),
-//               histogram of (window, |d|) bucket sizes      [global atomics]
-//   scan        exclusive scan of the histogram -> bucket offsets
-//   k_scatter   one thread per scalar: place (base index | sign) into its
-//               bucket's slice of the entry array (counting sort)
+//   k_part_count   per tile of 4096 scalars: signed c-bit digits (|d| <= 2^(c-1)), LDS
+//               histogram of the entries per coarse partition of the (window, |d|) bucket ids
+//   scan        exclusive scan of the partition-major tile counts -> record offsets
+//   k_part_scatter  the same digits again: (base index | sign, low bucket bits) records into
+//               the tile's slice of its partition, through LDS cursors
+//   k_part_sort one workgroup per partition: LDS counting sort by the low bucket bits -> the
+//               entry array, counts[bucket] and offsets[bucket]   [no global atomics anywhere]
+//   k_derive_*  a sparser density map over the same scalars: stable compaction of a sorted
+//               entry array instead of a second sort
 //   k_accumulate one thread per fixed-size SEGMENT of S sorted entries:
 //               mixed XYZZ additions of the gathered affine bases; perfectly
 //               load balanced whatever the digit distribution.  Partial sums
@@ -100,6 +104,12 @@ static void exclusive_scan_b(const uint32_t* in, uint32_t* out, size_t n, uint32
 
 void exclusive_scan(const uint32_t* in, uint32_t* out, size_t n, uint32_t* scratch, hipStream_t st) {
   exclusive_scan_b(in, out, n, scratch, st, nullptr);
+}
+
+// the dn form as derive_sorted runs it, for its self-test (bh_selftest_scan)
+void exclusive_scan_bounded(const uint32_t* in, uint32_t* out, size_t n, uint32_t* scratch, hipStream_t st,
+                            const uint32_t* dn) {
+  exclusive_scan_b(in, out, n, scratch, st, dn);
 }
 
 // ----------------------------------------------------------------- scalars
@@ -297,7 +307,9 @@ MsmShape msm_shape_table(size_t n, int c) {
 static constexpr int PT_TILE = 4096;  // scalars per tile
 
 // [plo, phi): the partitions a bucket shard keeps (MsmShape::bk_lo); digits outside are skipped by
-// both passes, so the scan leaves their partitions empty and k_part_sort writes zero counts there
+// both passes, and k_part_sort is launched for [plo, phi) alone: counts and offsets of the other
+// partitions' buckets are not written (but for offsets[bk_hi] and offsets[nbt], the shard's entry
+// count); the consumers read only the shard's range (tests/test_gpu_digit_sort.py pins this)
 __global__ void __launch_bounds__(256) k_part_count(const uint32_t* scalars, size_t n, const int32_t* idx,
                                                     DigitCfg cfg, int lo_bits, uint32_t P, uint32_t ntiles,
                                                     uint32_t plo, uint32_t phi, uint32_t* tilecounts) {

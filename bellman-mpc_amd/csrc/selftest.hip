@@ -1,8 +1,9 @@
 // Device self-tests of field arithmetic whose correctness rests on hand-derived bounds
 // (tests/test_gpu_selftest.py; not part of the public ABI, declared in api_internal.h), of the
 // field predicates and conversions (bh_selftest_field_misc), and the validated entry to the
-// accumulation kernels on an ordered entry list (bh_selftest_accumulate).  The group law's
-// self-test has units of its own (selftest_group.cuh).
+// accumulation kernels on an ordered entry list (bh_selftest_accumulate), and the validated entries
+// to the layer that produces such lists (bh_selftest_digit_sort and the four after it, at the end).
+// The group law's self-test has units of its own (selftest_group.cuh).
 //
 // fe2_mul_sub_kara (field.cuh; Fp2Ops::mul_sub_lazy, the G2 mixed addition's Y3 = R (Q - X3) - Y1
 // PPP under one Montgomery reduction per half) keeps signed Karatsuba column sums in a biased
@@ -11,6 +12,8 @@
 // a*b - c*d as two full Fp2 products and a subtraction (the path it replaced), on caller-chosen
 // operands -- the test drives both at the stated maxima and where the result is negative before
 // the fix-up, against host big integers.
+#include <algorithm>
+
 #include "api_internal.h"
 
 namespace {
@@ -231,5 +234,196 @@ extern "C" bh_status bh_selftest_fp2_mul_sub(int device, const uint32_t* in, siz
                      din.as<uint32_t>(), dout.as<uint32_t>(), (uint32_t)n);
   BH_TRY_HIP(hipGetLastError());
   BH_TRY_HIP(hipMemcpy(out, dout.p, out_b, hipMemcpyDeviceToHost));
+  return BH_OK;
+}
+
+// ------------------------------------------------------------------ scalars -> sorted entries
+// The layer between a caller's scalars and the accumulation kernels (msm_common.hip), driven
+// through the host functions of msm.h unchanged on host arrays (tests/test_gpu_digit_sort.py
+// against tests/digit_sort_model.py).  The kernels index memory from these arrays, so each entry
+// validates them and launches nothing on a violation; device buffers are sized by the library's
+// own functions and every output starts as 0xFF bytes.
+namespace {
+constexpr size_t SORT_CAP_N = (size_t)1 << 16;   // scalars / index-map words
+constexpr size_t SORT_CAP_E = (size_t)1 << 23;   // entries (2^16 scalars x 128 windows at c = 2)
+constexpr size_t SCAN_CAP_N = (size_t)1 << 21;
+
+hipError_t alloc_ff(bh::DevBuf& b, size_t words) {
+  hipError_t e = b.alloc(words * 4);
+  if (e == hipSuccess && words) e = hipMemset(b.p, 0xFF, words * 4);
+  return e;
+}
+hipError_t alloc_copy(bh::DevBuf& b, const void* src, size_t bytes) {
+  hipError_t e = b.alloc(bytes);
+  if (e == hipSuccess && bytes) e = hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
+  return e;
+}
+// a base index b is usable when b * W + w < 2^31 (bit 31 of an entry is the sign)
+bool idx_in_range(const int32_t* idx, size_t n, uint32_t W) {
+  const int64_t lim = ((int64_t)1 << 31) / (int64_t)W;
+  for (size_t i = 0; i < n; i++)
+    if (idx[i] < -1 || (int64_t)idx[i] >= lim) return false;
+  return true;
+}
+}  // namespace
+
+// sort_entries, then max_span over [red_lo, red_lo + Wb * red_nb) as the prover's sort_job calls
+// them, for the shape msm_shape(n, c) (pre = 0) or msm_shape_table(n, c) (pre = 1) with segment
+// length S and, when bk_lo | bk_hi, the bucket shard [bk_lo, bk_hi).  scalars: n x 8 LE words;
+// idx: n base indices (-1 = absent) or null for base_offset + i.  Returns entries[n * W],
+// counts[nbt], offsets[nbt + 1] (nbt = Wb * NB), the span words and their number.
+extern "C" bh_status bh_selftest_digit_sort(int device, const uint32_t* scalars, size_t n, const int32_t* idx,
+                                            uint32_t base_offset, int c, int pre, uint32_t bk_lo, uint32_t bk_hi,
+                                            uint32_t S, uint32_t* entries, uint32_t* counts, uint32_t* offsets,
+                                            uint32_t* span_words, uint32_t* n_span_words) {
+  if (c < 2 || c > 24 || (pre != 0 && pre != 1)) return BH_ERR_INVALID_ARGUMENT;
+  if (n > SORT_CAP_N || (n && (!scalars || !entries))) return BH_ERR_INVALID_ARGUMENT;
+  if (!counts || !offsets || !span_words || !n_span_words) return BH_ERR_INVALID_ARGUMENT;
+  if (S < 1 || S > (1u << 16)) return BH_ERR_INVALID_ARGUMENT;
+  bh::MsmShape sh = pre ? bh::msm_shape_table(n, c) : bh::msm_shape(n, c);
+  sh.S = (int)S;
+  const size_t E = n * (size_t)sh.W, nbt = (size_t)sh.Wb * sh.NB;
+  if (E >= ((size_t)1 << 31)) return BH_ERR_INVALID_ARGUMENT;
+  if (idx ? !idx_in_range(idx, n, (uint32_t)sh.W)
+          : (uint64_t)base_offset + n > (((uint64_t)1 << 31) / (uint64_t)sh.W))
+    return BH_ERR_INVALID_ARGUMENT;
+  if (bk_lo || bk_hi) {
+    const uint32_t G = std::max<uint32_t>(bh::BUCKET_SHARD_GRANULE, (uint32_t)sh.NB >> 12);
+    if (!pre || bk_lo >= bk_hi || bk_hi > (uint32_t)sh.NB || bk_lo % G || bk_hi % G) return BH_ERR_INVALID_ARGUMENT;
+    sh.bk_lo = bk_lo;
+    sh.bk_hi = bk_hi;
+  }
+  BH_TRY_HIP(hipSetDevice(device));
+  const size_t tc = bh::sort_tilecount_words(sh, n);
+  const size_t span_nbt = (size_t)sh.Wb * sh.red_nb();
+  const uint32_t g = bh::max_span_blocks(span_nbt);
+  bh::DevBuf dsc, didx, dtc, dts, drecs, dent, dcnt, doff, dspan;
+  BH_TRY_HIP(alloc_copy(dsc, scalars, n * 32));
+  if (idx) BH_TRY_HIP(alloc_copy(didx, idx, n * 4));
+  BH_TRY_HIP(alloc_ff(dtc, tc));
+  BH_TRY_HIP(alloc_ff(dts, bh::scan_scratch_words(tc) + 16));
+  BH_TRY_HIP(alloc_ff(drecs, 2 * E));
+  BH_TRY_HIP(alloc_ff(dent, E));
+  BH_TRY_HIP(alloc_ff(dcnt, nbt + 1));
+  BH_TRY_HIP(alloc_ff(doff, nbt + 1));
+  BH_TRY_HIP(alloc_ff(dspan, bh::MAX_SPAN_BLOCKS));
+  BH_TRY_HIP(bh::sort_entries(dsc.as<uint32_t>(), n, idx ? didx.as<int32_t>() : nullptr, base_offset, sh,
+                              dtc.as<uint32_t>(), dts.as<uint32_t>(), drecs.as<uint2>(), dent.as<uint32_t>(),
+                              dcnt.as<uint32_t>(), doff.as<uint32_t>(), nullptr));
+  BH_TRY_HIP(bh::max_span(dcnt.as<uint32_t>() + sh.red_lo(), doff.as<uint32_t>() + sh.red_lo(), span_nbt, S,
+                          dspan.as<uint32_t>(), nullptr, nullptr));
+  BH_TRY_HIP(hipDeviceSynchronize());
+  if (E) BH_TRY_HIP(hipMemcpy(entries, dent.p, E * 4, hipMemcpyDeviceToHost));
+  BH_TRY_HIP(hipMemcpy(counts, dcnt.p, nbt * 4, hipMemcpyDeviceToHost));
+  BH_TRY_HIP(hipMemcpy(offsets, doff.p, (nbt + 1) * 4, hipMemcpyDeviceToHost));
+  BH_TRY_HIP(hipMemcpy(span_words, dspan.p, (size_t)g * 4, hipMemcpyDeviceToHost));
+  *n_span_words = g;
+  return BH_OK;
+}
+
+// derive_sorted on a source layout given as host arrays: src_entries[Emax], src_offsets[nbt + 1]
+// (read at [b0, b1] and at nbt, the source's entry count: non-decreasing there and <= Emax),
+// every source entry's base inside [src_off, src_off + n_idx), the target map idx[n_idx] (-1 =
+// absent).  b1 = 0 stands for nbt, as in derive_sorted.  Returns dst_entries[Emax],
+// dst_counts[nbt], dst_offsets[nbt + 1].
+extern "C" bh_status bh_selftest_derive_sorted(int device, const uint32_t* src_entries, size_t Emax,
+                                               const uint32_t* src_offsets, size_t nbt, int pre, uint32_t W,
+                                               uint32_t src_off, const int32_t* idx, size_t n_idx, size_t b0,
+                                               size_t b1, uint32_t* dst_entries, uint32_t* dst_counts,
+                                               uint32_t* dst_offsets) {
+  if (!src_entries || !src_offsets || !idx || !dst_entries || !dst_counts || !dst_offsets)
+    return BH_ERR_INVALID_ARGUMENT;
+  if (!Emax || Emax > SORT_CAP_E || !nbt || nbt > SORT_CAP_E || !n_idx || n_idx > SORT_CAP_N)
+    return BH_ERR_INVALID_ARGUMENT;
+  if ((pre != 0 && pre != 1) || W < 1 || W > 128) return BH_ERR_INVALID_ARGUMENT;
+  if (b1 == 0) b1 = nbt;
+  if (b0 > b1 || b1 > nbt) return BH_ERR_INVALID_ARGUMENT;
+  const size_t E = src_offsets[nbt];
+  if (E > Emax || src_offsets[b1] > E) return BH_ERR_INVALID_ARGUMENT;
+  for (size_t b = b0; b < b1; b++)
+    if (src_offsets[b] > src_offsets[b + 1]) return BH_ERR_INVALID_ARGUMENT;
+  if (!idx_in_range(idx, n_idx, W)) return BH_ERR_INVALID_ARGUMENT;
+  for (size_t j = 0; j < E; j++) {
+    const uint32_t v = src_entries[j] & 0x7fffffffu;
+    const uint32_t base = pre ? v / W : v;
+    if (base < src_off || (size_t)(base - src_off) >= n_idx) return BH_ERR_INVALID_ARGUMENT;
+  }
+  BH_TRY_HIP(hipSetDevice(device));
+  bh::DevBuf dse, dso, didx, dpos, dscr, dent, dcnt, doff;
+  BH_TRY_HIP(alloc_copy(dse, src_entries, Emax * 4));
+  BH_TRY_HIP(alloc_copy(dso, src_offsets, (nbt + 1) * 4));
+  BH_TRY_HIP(alloc_copy(didx, idx, n_idx * 4));
+  BH_TRY_HIP(alloc_ff(dpos, Emax + 1));
+  BH_TRY_HIP(alloc_ff(dscr, bh::derive_scratch_words(Emax)));
+  BH_TRY_HIP(alloc_ff(dent, Emax));
+  BH_TRY_HIP(alloc_ff(dcnt, nbt + 1));
+  BH_TRY_HIP(alloc_ff(doff, nbt + 1));
+  BH_TRY_HIP(bh::derive_sorted(dse.as<uint32_t>(), dso.as<uint32_t>(), nbt, Emax, pre, W, src_off, didx.as<int32_t>(),
+                               dpos.as<uint32_t>(), dscr.as<uint32_t>(), dent.as<uint32_t>(), dcnt.as<uint32_t>(),
+                               doff.as<uint32_t>(), nullptr, b0, b1));
+  BH_TRY_HIP(hipDeviceSynchronize());
+  BH_TRY_HIP(hipMemcpy(dst_entries, dent.p, Emax * 4, hipMemcpyDeviceToHost));
+  BH_TRY_HIP(hipMemcpy(dst_counts, dcnt.p, nbt * 4, hipMemcpyDeviceToHost));
+  BH_TRY_HIP(hipMemcpy(dst_offsets, doff.p, (nbt + 1) * 4, hipMemcpyDeviceToHost));
+  return BH_OK;
+}
+
+// exclusive_scan of in[n] in place (dn < 0), or the scan bounded by a device word holding dn
+// (elements 0 .. dn), in place as derive_sorted runs it; out[n] is the buffer afterwards
+extern "C" bh_status bh_selftest_scan(int device, const uint32_t* in, size_t n, int64_t dn, uint32_t* out) {
+  if ((n && (!in || !out)) || n > SCAN_CAP_N || dn < -1 || dn > (int64_t)0xffffffff) return BH_ERR_INVALID_ARGUMENT;
+  if (!n) return BH_OK;
+  BH_TRY_HIP(hipSetDevice(device));
+  bh::DevBuf dbuf, dscr, ddn;
+  const uint32_t dn_word = (uint32_t)dn;
+  BH_TRY_HIP(alloc_copy(dbuf, in, n * 4));
+  BH_TRY_HIP(alloc_ff(dscr, bh::scan_scratch_words(n) + 16));
+  BH_TRY_HIP(alloc_copy(ddn, &dn_word, 4));
+  if (dn < 0)
+    bh::exclusive_scan(dbuf.as<uint32_t>(), dbuf.as<uint32_t>(), n, dscr.as<uint32_t>(), nullptr);
+  else
+    bh::exclusive_scan_bounded(dbuf.as<uint32_t>(), dbuf.as<uint32_t>(), n, dscr.as<uint32_t>(), nullptr,
+                               ddn.as<uint32_t>());
+  BH_TRY_HIP(hipGetLastError());
+  BH_TRY_HIP(hipDeviceSynchronize());
+  BH_TRY_HIP(hipMemcpy(out, dbuf.p, n * 4, hipMemcpyDeviceToHost));
+  return BH_OK;
+}
+
+// scalars_prepare: in (8 LE words per scalar; 2^log_perm of them when log_perm > 0, then
+// n = 2^log_perm) -> out[n x 8]; mode 0 canonical words, 1 bls12_381 Montgomery, 2 device Montgomery
+extern "C" bh_status bh_selftest_scalars_prepare(int device, const uint32_t* in, size_t n, int mode, int log_perm,
+                                                 uint32_t* out) {
+  if ((n && (!in || !out)) || n > SORT_CAP_N || mode < 0 || mode > 2 || log_perm < 0 || log_perm > 16)
+    return BH_ERR_INVALID_ARGUMENT;
+  if (log_perm > 0 && n != ((size_t)1 << log_perm)) return BH_ERR_INVALID_ARGUMENT;
+  if (!n) return BH_OK;
+  BH_TRY_HIP(hipSetDevice(device));
+  bh::DevBuf din, dout;
+  BH_TRY_HIP(alloc_copy(din, in, n * 32));
+  BH_TRY_HIP(alloc_ff(dout, n * 8));
+  BH_TRY_HIP(bh::scalars_prepare(din.as<uint32_t>(), dout.as<uint32_t>(), n, mode, log_perm, nullptr));
+  BH_TRY_HIP(hipDeviceSynchronize());
+  BH_TRY_HIP(hipMemcpy(out, dout.p, n * 32, hipMemcpyDeviceToHost));
+  return BH_OK;
+}
+
+// density_index: words[ceil(n / 64)] -> idx[n]
+extern "C" bh_status bh_selftest_density_index(int device, const uint64_t* words, size_t n, uint32_t base_offset,
+                                               int32_t* idx) {
+  if ((n && (!words || !idx)) || n > 2 * SORT_CAP_N || (uint64_t)base_offset + n >= ((uint64_t)1 << 31))
+    return BH_ERR_INVALID_ARGUMENT;
+  if (!n) return BH_OK;
+  BH_TRY_HIP(hipSetDevice(device));
+  const size_t nwords = (n + 63) / 64;
+  bh::DevBuf dw, didx, dtmp, dscr;
+  BH_TRY_HIP(alloc_copy(dw, words, nwords * 8));
+  BH_TRY_HIP(alloc_ff(didx, n));
+  BH_TRY_HIP(alloc_ff(dtmp, nwords));
+  BH_TRY_HIP(alloc_ff(dscr, bh::scan_scratch_words(nwords) + 16));
+  BH_TRY_HIP(bh::density_index(dw.as<uint64_t>(), n, base_offset, didx.as<int32_t>(), dtmp.as<uint32_t>(),
+                               dscr.as<uint32_t>(), nullptr));
+  BH_TRY_HIP(hipDeviceSynchronize());
+  BH_TRY_HIP(hipMemcpy(idx, didx.p, n * 4, hipMemcpyDeviceToHost));
   return BH_OK;
 }
