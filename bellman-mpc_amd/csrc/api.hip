@@ -61,81 +61,47 @@ Fr fr_from_dev_packed(const uint32_t in[8]) {
 }
 
 // ------------------------------------------------------------------ device point conversion
-// canonical packed coordinates -> device Montgomery packed; optional on-curve check
-// G1 (G1F, curve.cuh): the same in G1's representation
-__global__ void __launch_bounds__(256) k_points_to_dev_g1(uint32_t* pts, size_t n, int check, uint32_t* bad) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  using F = G1F;
-  F::T r2;
-#pragma unroll
-  for (int k = 0; k < F::Cf::N; k++) r2.v[k] = F::Cf::R2[k];
-  F::T c[2];
-  uint32_t nz = 0;
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    uint32_t* w = pts + (i * 2 + k) * 12;
-#pragma unroll
-    for (int l = 0; l < 12; l++) nz |= w[l];
-    c[k] = F::reduce(F::mul(F::unpack(w), r2));
-    F::pack(c[k], w);
-  }
-  if (check && nz) {  // (0,0) encodes the identity (never on the curve), skip it
-    const F::T four = F::add(F::add(F::one(), F::one()), F::add(F::one(), F::one()));
-    const F::T lhs = F::sqr(c[1]);
-    const F::T rhs = F::add(F::mul(F::sqr(c[0]), c[0]), four);
-    if (!F::is_zero(F::template sub<8>(lhs, rhs))) atomicOr(bad, 1u);
-  }
-}
-
-template <bool G2>
+// canonical packed components -> device Montgomery packed, in place; optional on-curve check
+template <class C>
 __global__ void __launch_bounds__(256) k_points_to_dev(uint32_t* pts, size_t n, int check, uint32_t* bad) {
-  static_assert(G2, "G1 points: k_points_to_dev_g1");
+  using F = typename FieldOf<C>::F;
+  constexpr int NC = 2 * F::PACKED_WORDS / 12;  // Fp components per point
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  constexpr int NC = G2 ? 4 : 2;  // DFp coordinates per point
   DFp r2;
 #pragma unroll
-  for (int k = 0; k < 14; k++) r2.v[k] = FpCfg::R2[k];
+  for (int k = 0; k < FpCfg::N; k++) r2.v[k] = FpCfg::R2[k];
   DFp c[NC];
-#pragma unroll
-  for (int k = 0; k < NC; k++) {
-    DFp x = fe_unpack<FpCfg>(pts + (i * NC + k) * 12);
-    c[k] = fe_reduce_full<FpCfg>(fe_mul<FpCfg>(x, r2));
-    fe_pack<FpCfg>(c[k], pts + (i * NC + k) * 12);
-  }
   uint32_t nz = 0;
 #pragma unroll
-  for (int k = 0; k < NC; k++)
+  for (int k = 0; k < NC; k++) {
+    uint32_t* w = pts + (i * NC + k) * 12;
 #pragma unroll
-    for (int l = 0; l < 14; l++) nz |= c[k].v[l];
-  if (check && nz) {  // (0,0) encodes the identity (never on the curve), skip it
-    DFp four = fe_add<FpCfg>(fe_add<FpCfg>(fe_one<FpCfg>(), fe_one<FpCfg>()),
-                            fe_add<FpCfg>(fe_one<FpCfg>(), fe_one<FpCfg>()));
-    bool ok;
-    if (!G2) {
-      DFp lhs = fe_sqr<FpCfg>(c[1]);
-      DFp rhs = fe_add<FpCfg>(fe_mul<FpCfg>(fe_sqr<FpCfg>(c[0]), c[0]), four);
-      ok = fe_is_zero<FpCfg>(fe_sub<FpCfg, 8>(lhs, rhs));
-    } else {
-      DFp2 x{c[0], c[1]}, y{c[2], c[3]};
-      DFp2 lhs = Fp2Ops::sqr(y);
-      DFp2 x3 = Fp2Ops::mul(Fp2Ops::sqr(x), x);
-      DFp2 rhs{fe_add<FpCfg>(x3.c0, four), fe_add<FpCfg>(x3.c1, four)};
-      DFp2 d = Fp2Ops::sub<16>(lhs, rhs);
-      ok = Fp2Ops::is_zero(d);
+    for (int l = 0; l < 12; l++) nz |= w[l];
+    c[k] = fe_reduce_full<FpCfg>(fe_mul<FpCfg>(fe_unpack<FpCfg>(w), r2));
+    fe_pack<FpCfg>(c[k], w);
+  }
+  if (check && nz) {  // the all-zero record encodes the identity (never on the curve), skip it
+    typename F::T x, y, b = F::add(F::add(F::one(), F::one()), F::add(F::one(), F::one()));
+    if constexpr (NC == 2) {  // y^2 = x^3 + 4 over Fp
+      x = c[0]; y = c[1];
+    } else {                  // y^2 = x^3 + 4 + 4u over Fp2
+      x = DFp2{c[0], c[1]}; y = DFp2{c[2], c[3]};
+      b.c1 = b.c0;
     }
-    if (!ok) atomicOr(bad, 1u);
+    // field.cuh's bounds: a product is < MB p = 2p and b's components are < 4p, so the subtrahend
+    // is < 6p and K = 8 covers it; the difference is < 10p, far below is_zero's 128p
+    static_assert(F::MB + 4 <= 8, "the subtraction constant below");
+    if (!F::is_zero(F::template sub<8>(F::sqr(y), F::add(F::mul(F::sqr(x), x), b)))) atomicOr(bad, 1u);
   }
 }
 
 // Prime-order subgroup check of Parameters::read(checked) (G1Affine/G2Affine::
 // from_uncompressed reject points that are not torsion-free): [r]P == O by a
 // double-and-add over the bits of r in XYZZ coordinates.  Runs on the device-form points.
-template <bool G2>
+template <class C>
 __global__ void __launch_bounds__(256) k_subgroup_check(const uint32_t* pts, size_t n, uint32_t* bad) {
-  using C = typename std::conditional<G2, G2Ops, G1Ops>::type;
-  using F = typename std::conditional<G2, Fp2Ops, G1F>::type;
+  using F = typename FieldOf<C>::F;
   constexpr int PW = F::PACKED_WORDS;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -158,236 +124,158 @@ __global__ void __launch_bounds__(256) k_subgroup_check(const uint32_t* pts, siz
 }
 
 // ------------------------------------------------------------------ SRS
-// host affine points -> device (packed canonical words, then device conversion)
-bh_status srs_upload_affine(bh_ctx* ctx, int group, const void* host_pts, size_t n, bh_srs* out) {
+// canonical packed words of out->n points -> out->pts in device form; checked: every point is on
+// the curve and in the subgroup
+template <class G>
+static bh_status srs_convert(bh_ctx* ctx, const std::vector<uint32_t>& w, int checked, bh_srs* out) {
+  using C = typename G::Ops;
+  const size_t n = out->n;
   out->ctx = ctx;
-  out->group = group;
-  out->n = n;
-  out->identity_idx.clear();
-  const int words = group == BH_G1 ? 24 : 48;
-  std::vector<uint32_t> w((size_t)n * words);
-  for (size_t i = 0; i < n; i++) {
-    uint32_t* d = &w[i * words];
-    if (group == BH_G1) {
-      const AffinePt<Fp>& a = reinterpret_cast<const AffinePt<Fp>*>(host_pts)[i];
-      if (a.infinity) { out->identity_idx.push_back(i); memset(d, 0, words * 4); continue; }
-      uint64_t raw[6];
-      to_int(a.x, raw); memcpy(d, raw, 48);
-      to_int(a.y, raw); memcpy(d + 12, raw, 48);
-    } else {
-      const AffinePt<Fp2>& a = reinterpret_cast<const AffinePt<Fp2>*>(host_pts)[i];
-      if (a.infinity) { out->identity_idx.push_back(i); memset(d, 0, words * 4); continue; }
-      uint64_t raw[6];
-      to_int(a.x.c0, raw); memcpy(d, raw, 48);
-      to_int(a.x.c1, raw); memcpy(d + 12, raw, 48);
-      to_int(a.y.c0, raw); memcpy(d + 24, raw, 48);
-      to_int(a.y.c1, raw); memcpy(d + 36, raw, 48);
-    }
+  out->group = G::ID;
+  BH_TRY_HIP(out->pts.alloc(std::max<size_t>(n, 1) * G::WORDS * 4));
+  if (!n) return BH_OK;
+  DevBuf bad;
+  if (checked) {
+    BH_TRY_HIP(bad.alloc(4));
+    BH_TRY_HIP(hipMemsetAsync(bad.p, 0, 4, ctx->stream));
   }
-  BH_TRY_HIP(out->pts.alloc(std::max<size_t>(n, 1) * words * 4));
-  if (n) {
-    BH_TRY_HIP(hipMemcpyAsync(out->pts.p, w.data(), n * words * 4, hipMemcpyHostToDevice, ctx->stream));
-    unsigned blocks = (unsigned)((n + 255) / 256);
-    if (group == BH_G1)
-      hipLaunchKernelGGL(k_points_to_dev_g1, dim3(blocks), dim3(256), 0, ctx->stream, out->pts.as<uint32_t>(), n,
-                         0, (uint32_t*)nullptr);
-    else
-      hipLaunchKernelGGL(k_points_to_dev<true>, dim3(blocks), dim3(256), 0, ctx->stream, out->pts.as<uint32_t>(), n,
-                         0, (uint32_t*)nullptr);
+  BH_TRY_HIP(hipMemcpyAsync(out->pts.p, w.data(), n * G::WORDS * 4, hipMemcpyHostToDevice, ctx->stream));
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(k_points_to_dev<C>, dim3(blocks), dim3(256), 0, ctx->stream, out->pts.as<uint32_t>(), n, checked,
+                     bad.as<uint32_t>());
+  BH_TRY_HIP(hipGetLastError());
+  uint32_t hbad = 0;
+  if (checked) {
+    hipLaunchKernelGGL(k_subgroup_check<C>, dim3(blocks), dim3(256), 0, ctx->stream, out->pts.as<uint32_t>(), n,
+                       bad.as<uint32_t>());
     BH_TRY_HIP(hipGetLastError());
-    BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    BH_TRY_HIP(hipMemcpyAsync(&hbad, bad.p, 4, hipMemcpyDeviceToHost, ctx->stream));
   }
+  BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  if (hbad & 1u) return BH_ERR_NOT_ON_CURVE;
+  if (hbad & 2u) return BH_ERR_NOT_IN_SUBGROUP;
   return BH_OK;
 }
+
+// host affine points -> device
+template <class T>
+bh_status srs_upload_affine(bh_ctx* ctx, const AffinePt<T>* pts, size_t n, bh_srs* out) {
+  using G = HostOfField<T>;
+  out->n = n;
+  out->identity_idx.clear();
+  std::vector<uint32_t> w(n * G::WORDS);
+  for (size_t i = 0; i < n; i++) {
+    if (pts[i].infinity) out->identity_idx.push_back(i);
+    G::canonical_words(pts[i], &w[i * G::WORDS]);
+  }
+  return srs_convert<G>(ctx, w, 0, out);
+}
+template bh_status srs_upload_affine<Fp>(bh_ctx*, const AffinePt<Fp>*, size_t, bh_srs*);
+template bh_status srs_upload_affine<Fp2>(bh_ctx*, const AffinePt<Fp2>*, size_t, bh_srs*);
 
 // parse n uncompressed encodings; returns BH_ERR_INVALID_ENCODING / BH_ERR_NOT_ON_CURVE
 bh_status srs_from_bytes(bh_ctx* ctx, int group, const uint8_t* bytes, size_t n, int checked,
                                 bool reject_identity, bh_srs* out) {
-  const size_t pb = group == BH_G1 ? 96 : 192;
-  const int words = group == BH_G1 ? 24 : 48;
-  out->ctx = ctx;
-  out->group = group;
-  out->n = n;
-  out->identity_idx.clear();
-  std::vector<uint32_t> w((size_t)n * words);
-  for (size_t i = 0; i < n; i++) {
-    const uint8_t* b = bytes + i * pb;
-    uint32_t* d = &w[i * words];
-    const uint8_t flags = b[0] >> 5;
-    if ((flags & 0x4) || (flags & 0x1)) return BH_ERR_INVALID_ENCODING;
-    if (flags & 0x2) {
-      for (size_t k = 0; k < pb; k++)
-        if ((k == 0 ? (b[0] & 0x1F) : b[k]) != 0) return BH_ERR_INVALID_ENCODING;
-      if (reject_identity) return BH_ERR_INVALID_ENCODING;
-      out->identity_idx.push_back(i);
-      memset(d, 0, words * 4);
-      continue;
-    }
-    // each 48-byte big-endian field element -> 12 LE words, canonical check
-    const int nf = group == BH_G1 ? 2 : 4;
-    for (int f = 0; f < nf; f++) {
-      // G2 wire order: x.c1, x.c0, y.c1, y.c0 ; device order: x.c0, x.c1, y.c0, y.c1
-      int dst = group == BH_G1 ? f : (f ^ 1);
-      const uint8_t* src = b + 48 * f;
-      uint64_t raw[6] = {0};
-      for (int k = 0; k < 48; k++) {
-        uint8_t byte = src[k];
-        if (f == 0 && k == 0) byte &= 0x1F;
-        raw[(47 - k) / 8] |= (uint64_t)byte << (8 * ((47 - k) % 8));
+  return with_group(group, [&](auto g) -> bh_status {
+    using G = decltype(g);
+    using T = typename G::Field;
+    out->n = n;
+    out->identity_idx.clear();
+    std::vector<uint32_t> w(n * G::WORDS);
+    for (size_t i = 0; i < n; i++) {
+      const uint8_t* b = bytes + i * G::WIRE;
+      uint32_t* d = &w[i * G::WORDS];
+      const uint8_t flags = b[0] >> 5;
+      if ((flags & 0x4) || (flags & 0x1)) return BH_ERR_INVALID_ENCODING;
+      if (flags & 0x2) {
+        for (size_t k = 0; k < G::WIRE; k++)
+          if ((k == 0 ? (b[0] & 0x1F) : b[k]) != 0) return BH_ERR_INVALID_ENCODING;
+        if (reject_identity) return BH_ERR_INVALID_ENCODING;
+        out->identity_idx.push_back(i);
+        memset(d, 0, G::WORDS * 4);
+        continue;
       }
-      if (geq_p<6>(raw)) return BH_ERR_INVALID_ENCODING;
-      memcpy(d + 12 * dst, raw, 48);
+      // each 48-byte big-endian wire slot -> the 12 LE words of its component, canonical check
+      for (int f = 0; f < COMPONENTS<T>; f++) {
+        const uint8_t* src = b + 48 * f;
+        uint64_t raw[6] = {0};
+        for (int k = 0; k < 48; k++) {
+          uint8_t byte = src[k];
+          if (f == 0 && k == 0) byte &= 0x1F;
+          raw[(47 - k) / 8] |= (uint64_t)byte << (8 * ((47 - k) % 8));
+        }
+        if (geq_p<6>(raw)) return BH_ERR_INVALID_ENCODING;
+        memcpy(d + 12 * wire_component<T>(f), raw, 48);
+      }
     }
-  }
-  BH_TRY_HIP(out->pts.alloc(std::max<size_t>(n, 1) * words * 4));
-  if (n) {
-    DevBuf bad;
-    BH_TRY_HIP(bad.alloc(4));
-    BH_TRY_HIP(hipMemsetAsync(bad.p, 0, 4, ctx->stream));
-    BH_TRY_HIP(hipMemcpyAsync(out->pts.p, w.data(), n * words * 4, hipMemcpyHostToDevice, ctx->stream));
-    unsigned blocks = (unsigned)((n + 255) / 256);
-    if (group == BH_G1)
-      hipLaunchKernelGGL(k_points_to_dev_g1, dim3(blocks), dim3(256), 0, ctx->stream, out->pts.as<uint32_t>(), n,
-                         checked, bad.as<uint32_t>());
-    else
-      hipLaunchKernelGGL(k_points_to_dev<true>, dim3(blocks), dim3(256), 0, ctx->stream, out->pts.as<uint32_t>(), n,
-                         checked, bad.as<uint32_t>());
-    BH_TRY_HIP(hipGetLastError());
-    if (checked) {
-      if (group == BH_G1)
-        hipLaunchKernelGGL(k_subgroup_check<false>, dim3(blocks), dim3(256), 0, ctx->stream, out->pts.as<uint32_t>(),
-                           n, bad.as<uint32_t>());
-      else
-        hipLaunchKernelGGL(k_subgroup_check<true>, dim3(blocks), dim3(256), 0, ctx->stream, out->pts.as<uint32_t>(),
-                           n, bad.as<uint32_t>());
-      BH_TRY_HIP(hipGetLastError());
-    }
-    uint32_t hbad = 0;
-    BH_TRY_HIP(hipMemcpyAsync(&hbad, bad.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
-    if (hbad & 1u) return BH_ERR_NOT_ON_CURVE;
-    if (hbad & 2u) return BH_ERR_NOT_IN_SUBGROUP;
-  }
+    return srs_convert<G>(ctx, w, checked, out);
+  });
+}
+
+template <class G>
+bh_status download_points(const bh_srs& v, size_t n, std::vector<typename G::Affine>* out) {
+  std::vector<uint32_t> w(n * G::WORDS);
+  if (n) BH_TRY_HIP(hipMemcpy(w.data(), v.pts.p, n * G::WORDS * 4, hipMemcpyDeviceToHost));
+  out->resize(n);
+  for (size_t i = 0; i < n; i++) (*out)[i] = G::from_dev_words(&w[i * G::WORDS]);
+  for (size_t i : v.identity_idx)
+    if (i < n) (*out)[i].infinity = true;
   return BH_OK;
 }
+template bh_status download_points<G1Host>(const bh_srs&, size_t, std::vector<AffinePt<Fp>>*);
+template bh_status download_points<G2Host>(const bh_srs&, size_t, std::vector<AffinePt<Fp2>>*);
 
 // ------------------------------------------------------------------ MSM glue
-static inline Fp fp_from_dev_limbs(const uint32_t* limbs14) {
-  // unpacked 29-bit limbs (canonical) -> packed words -> host
-  uint32_t words[12] = {0};
-  for (int i = 0; i < 14; i++) {
-    const int bit = 29 * i;
-    const int wi = bit >> 5, sh = bit & 31;
-    uint64_t v = (uint64_t)limbs14[i] << sh;
-    words[wi] |= (uint32_t)v;
-    if (wi + 1 < 12) words[wi + 1] |= (uint32_t)(v >> 32);
-  }
-  return fp_from_dev_words(words);
-}
-
-// G1 (G1F: 13 balanced 30-bit digits or 14 x 29-bit limbs, R = 2^(N*BITS)): a canonical
-// coordinate's limbs (C::reduce) -> packed words -> host
-Fp fp_from_dev_words_g1(const uint32_t* w) {
-  using Cf = G1F::Cf;
-  return fp_from_dev_words_r<Cf::N * Cf::BITS>(w);
-}
-Fp fp_from_dev_g1(const G1F::T& x) {
-  using Cf = G1F::Cf;
-  uint32_t words[12] = {0};
-  int64_t carry = 0;
-  for (int i = 0; i < Cf::N; i++) {  // (signed) digits -> unsigned BITS-bit limbs of the value in [0, p)
-    const int64_t s = (int64_t)x.v[i] + carry;
-    const uint32_t limb = (uint32_t)(s & (int64_t)Cf::MASK);
-    carry = s >> Cf::BITS;
-    const int bit = Cf::BITS * i;
-    const int wi = bit >> 5, sh = bit & 31;
-    const uint64_t v = (uint64_t)limb << sh;
-    words[wi] |= (uint32_t)v;
-    if (wi + 1 < 12) words[wi + 1] |= (uint32_t)(v >> 32);
-  }
-  return fp_from_dev_words_g1(words);
-}
-
-static Jac<Fp> g1_from_xyzz(const XYZZ<G1F>& p) {
-  return xyzz_to_jac(fp_from_dev_g1(p.X), fp_from_dev_g1(p.Y), fp_from_dev_g1(p.ZZ), fp_from_dev_g1(p.ZZZ));
-}
 // window sums -> the multiexp (Horner over the Wb windows, c doublings each; multiexp.rs:244-249),
 // or, for one shared bucket window, out[0] + 2^shift * out[1] (msm_back's split reduction)
-Jac<Fp> combine_g1(const XYZZ<G1F>* ws, const MsmShape& sh) {
-  const int shift = reduce_split_shift(sh, false);
+template <class G>
+typename G::Jacobian combine(const XYZZ<typename G::DevField>* ws, const MsmShape& sh) {
+  using J = typename G::Jacobian;
+  const int shift = reduce_split_shift(sh, G::ID == BH_G2);
   if (shift >= 0) {
-    Jac<Fp> z = g1_from_xyzz(ws[1]);
+    J z = G::from_xyzz(ws[1]);
     for (int k = 0; k < shift; k++) z = jac_dbl(z);
-    z = jac_add(g1_from_xyzz(ws[0]), z);
+    z = jac_add(G::from_xyzz(ws[0]), z);
     if (sh.bucket_shard() && sh.bk_lo) {  // + bk_lo * (plain sum of the range's buckets)
       const uint64_t k[1] = {sh.bk_lo};
-      z = jac_add(z, jac_mul(g1_from_xyzz(ws[2]), k, 1));
+      z = jac_add(z, jac_mul(G::from_xyzz(ws[2]), k, 1));
     }
     return z;
   }
-  Jac<Fp> acc = jac_identity<Fp>();
+  J acc = jac_identity<typename G::Field>();
   for (int w = sh.Wb - 1; w >= 0; w--) {
     for (int k = 0; k < sh.c; k++) acc = jac_dbl(acc);
-    acc = jac_add(acc, g1_from_xyzz(ws[w]));
+    acc = jac_add(acc, G::from_xyzz(ws[w]));
   }
   return acc;
 }
-static inline bh::Fp2 fp2_from_dev(const DFp2& v) {
-  return bh::Fp2{fp_from_dev_limbs(v.c0.v), fp_from_dev_limbs(v.c1.v)};
-}
-static Jac<bh::Fp2> g2_from_xyzz(const XYZZ<Fp2Ops>& p) {
-  return xyzz_to_jac(fp2_from_dev(p.X), fp2_from_dev(p.Y), fp2_from_dev(p.ZZ), fp2_from_dev(p.ZZZ));
-}
-Jac<bh::Fp2> combine_g2(const XYZZ<Fp2Ops>* ws, const MsmShape& sh) {
-  const int shift = reduce_split_shift(sh, true);
-  if (shift >= 0) {
-    Jac<bh::Fp2> z = g2_from_xyzz(ws[1]);
-    for (int k = 0; k < shift; k++) z = jac_dbl(z);
-    z = jac_add(g2_from_xyzz(ws[0]), z);
-    if (sh.bucket_shard() && sh.bk_lo) {  // + bk_lo * (plain sum of the range's buckets)
-      const uint64_t k[1] = {sh.bk_lo};
-      z = jac_add(z, jac_mul(g2_from_xyzz(ws[2]), k, 1));
-    }
-    return z;
-  }
-  Jac<bh::Fp2> acc = jac_identity<bh::Fp2>();
-  for (int w = sh.Wb - 1; w >= 0; w--) {
-    for (int k = 0; k < sh.c; k++) acc = jac_dbl(acc);
-    acc = jac_add(acc, g2_from_xyzz(ws[w]));
-  }
-  return acc;
-}
+template Jac<Fp> combine<G1Host>(const XYZZ<G1F>*, const MsmShape&);
+template Jac<Fp2> combine<G2Host>(const XYZZ<Fp2Ops>*, const MsmShape&);
 
-static MsmTiming g_no_timing;
+static MsmWorkspace<G1Ops>& ctx_ws(bh_ctx* ctx, G1Host) { return ctx->g1ws; }
+static MsmWorkspace<G2Ops>& ctx_ws(bh_ctx* ctx, G2Host) { return ctx->g2ws; }
 
-bh_status msm_g1_device(bh_ctx* ctx, const bh_srs* bases, size_t base_offset, const uint32_t* d_scalars, size_t n,
-                        const int32_t* d_idx, Jac<Fp>* out, float* acc_ms) {
-  if (n == 0) { *out = jac_identity<Fp>(); return BH_OK; }
+template <class G>
+bh_status msm_device(bh_ctx* ctx, const bh_srs* bases, size_t base_offset, const uint32_t* d_scalars, size_t n,
+                     const int32_t* d_idx, typename G::Jacobian* out, float* acc_ms) {
+  using C = typename G::Ops;
+  if (n == 0) { *out = jac_identity<typename G::Field>(); return BH_OK; }
   MsmShape sh = msm_shape(n, ctx->window_override);
-  fit_segments<G1Ops>(sh, n);
+  fit_segments<C>(sh, n);
   MsmTiming tm;
   if (acc_ms) { tm.ev_acc_begin = ctx->ev[EV_MSM_ACC_BEGIN]; tm.ev_acc_end = ctx->ev[EV_MSM_ACC_END]; }
-  BH_TRY_HIP(msm_window_sums<G1Ops>(ctx->g1ws, ctx->stream, bases->pts.as<uint32_t>(), d_scalars, n, d_idx,
-                                    (uint32_t)base_offset, sh, acc_ms ? &tm : nullptr));
+  auto& ws = ctx_ws(ctx, G{});
+  BH_TRY_HIP(msm_window_sums<C>(ws, ctx->stream, bases->pts.as<uint32_t>(), d_scalars, n, d_idx, (uint32_t)base_offset,
+                                sh, acc_ms ? &tm : nullptr));
   BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
   if (acc_ms) { float t = 0; if (hipEventElapsedTime(&t, tm.ev_acc_begin, tm.ev_acc_end) == hipSuccess) *acc_ms += t; }
-  *out = combine_g1(ctx->g1ws.host_window_sums, sh);
+  *out = combine<G>(ws.host_window_sums, sh);
   return BH_OK;
 }
-bh_status msm_g2_device(bh_ctx* ctx, const bh_srs* bases, size_t base_offset, const uint32_t* d_scalars, size_t n,
-                        const int32_t* d_idx, Jac<bh::Fp2>* out, float* acc_ms) {
-  if (n == 0) { *out = jac_identity<bh::Fp2>(); return BH_OK; }
-  MsmShape sh = msm_shape(n, ctx->window_override);
-  fit_segments<G2Ops>(sh, n);
-  MsmTiming tm;
-  if (acc_ms) { tm.ev_acc_begin = ctx->ev[EV_MSM_ACC_BEGIN]; tm.ev_acc_end = ctx->ev[EV_MSM_ACC_END]; }
-  BH_TRY_HIP(msm_window_sums<G2Ops>(ctx->g2ws, ctx->stream, bases->pts.as<uint32_t>(), d_scalars, n, d_idx,
-                                    (uint32_t)base_offset, sh, acc_ms ? &tm : nullptr));
-  BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
-  if (acc_ms) { float t = 0; if (hipEventElapsedTime(&t, tm.ev_acc_begin, tm.ev_acc_end) == hipSuccess) *acc_ms += t; }
-  *out = combine_g2(ctx->g2ws.host_window_sums, sh);
-  return BH_OK;
-}
+template bh_status msm_device<G1Host>(bh_ctx*, const bh_srs*, size_t, const uint32_t*, size_t, const int32_t*, Jac<Fp>*,
+                                      float*);
+template bh_status msm_device<G2Host>(bh_ctx*, const bh_srs*, size_t, const uint32_t*, size_t, const int32_t*, Jac<Fp2>*,
+                                      float*);
 
 // bellman's window rule (multiexp.rs:267-271) -- only used for error semantics
 static int bellman_window(size_t n) {
@@ -1019,19 +907,16 @@ size_t bh_srs_len(const bh_srs* srs) { return srs ? srs->n : 0; }
 
 bh_status bh_srs_get(const bh_srs* srs, size_t i, uint8_t* out) {
   if (!srs || !out || i >= srs->n) return BH_ERR_INVALID_ARGUMENT;
-  const int words = srs->group == BH_G1 ? 24 : 48;
-  uint32_t w[48];
-  BH_TRY_HIP(hipMemcpy(w, srs->pts.as<uint32_t>() + i * words, words * 4, hipMemcpyDeviceToHost));
-  bool inf = std::find(srs->identity_idx.begin(), srs->identity_idx.end(), i) != srs->identity_idx.end();
-  if (srs->group == BH_G1) {
-    AffinePt<Fp> a{fp_from_dev_words_g1(w), fp_from_dev_words_g1(w + 12), inf};
-    g1_to_uncompressed(a, out);
-  } else {
-    AffinePt<bh::Fp2> a{bh::Fp2{fp_from_dev_words(w), fp_from_dev_words(w + 12)},
-                        bh::Fp2{fp_from_dev_words(w + 24), fp_from_dev_words(w + 36)}, inf};
-    g2_to_uncompressed(a, out);
-  }
-  return BH_OK;
+  const bool inf = std::find(srs->identity_idx.begin(), srs->identity_idx.end(), i) != srs->identity_idx.end();
+  return with_group(srs->group, [&](auto g) -> bh_status {
+    using G = decltype(g);
+    uint32_t w[G::WORDS];
+    BH_TRY_HIP(hipMemcpy(w, srs->pts.as<uint32_t>() + i * G::WORDS, G::WORDS * 4, hipMemcpyDeviceToHost));
+    typename G::Affine a = G::from_dev_words(w);
+    a.infinity = inf;
+    to_uncompressed(a, out);
+    return BH_OK;
+  });
 }
 
 // ---------------------------------------------------------------- multiexp
@@ -1079,16 +964,13 @@ bh_status bh_multiexp(bh_ctx* ctx, const bh_srs* bases, size_t base_offset, cons
                              ctx->dtmp.as<uint32_t>(), ctx->dscan.as<uint32_t>(), ctx->stream));
     d_idx = ctx->idx.as<int32_t>();
   }
-  if (bases->group == BH_G1) {
-    Jac<Fp> r;
-    if ((st = msm_g1_device(ctx, bases, base_offset, d_sc, n, d_idx, &r, nullptr))) return st;
-    g1_to_uncompressed(jac_to_affine(r), out);
-  } else {
-    Jac<bh::Fp2> r;
-    if ((st = msm_g2_device(ctx, bases, base_offset, d_sc, n, d_idx, &r, nullptr))) return st;
-    g2_to_uncompressed(jac_to_affine(r), out);
-  }
-  return BH_OK;
+  return with_group(bases->group, [&](auto g) -> bh_status {
+    using G = decltype(g);
+    typename G::Jacobian r;
+    if (bh_status e = msm_device<G>(ctx, bases, base_offset, d_sc, n, d_idx, &r, nullptr)) return e;
+    to_uncompressed(jac_to_affine(r), out);
+    return BH_OK;
+  });
 }
 
 // ---------------------------------------------------------------- EvaluationDomain

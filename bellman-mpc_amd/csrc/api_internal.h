@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../../include/bellman_hip.h"
-#include "host_arith.h"
+#include "group_host.h"
 #include "msm.h"
 #include "ntt.h"
 #include "staging.h"
@@ -442,17 +442,17 @@ void ctx_sync_all(bh_ctx* ctx);
 void fr_to_dev_limbs(const Fr& x, uint32_t out[9]);
 void fr_to_dev_packed(const Fr& x, uint32_t out[8]);
 Fr fr_from_dev_packed(const uint32_t in[8]);
-// G1 device coordinates (C::reduce output, G1F's limb or balanced-digit form; packed words) -> host
-Fp fp_from_dev_g1(const G1F::T& x);
-Fp fp_from_dev_words_g1(const uint32_t* w);
-// combine per-window sums (host Horner, multiexp.rs:244-249)
-Jac<Fp> combine_g1(const XYZZ<G1F>* ws, const MsmShape& sh);
-Jac<Fp2> combine_g2(const XYZZ<Fp2Ops>* ws, const MsmShape& sh);
+// window sums -> the multiexp (host Horner, multiexp.rs:244-249)
+template <class G>
+typename G::Jacobian combine(const XYZZ<typename G::DevField>* ws, const MsmShape& sh);
 // run one MSM whose scalars/index map are already on the device; returns result on host
-bh_status msm_g1_device(bh_ctx* ctx, const bh_srs* bases, size_t base_offset, const uint32_t* d_scalars, size_t n,
-                        const int32_t* d_idx, Jac<Fp>* out, float* acc_ms);
-bh_status msm_g2_device(bh_ctx* ctx, const bh_srs* bases, size_t base_offset, const uint32_t* d_scalars, size_t n,
-                        const int32_t* d_idx, Jac<Fp2>* out, float* acc_ms);
+template <class G>
+bh_status msm_device(bh_ctx* ctx, const bh_srs* bases, size_t base_offset, const uint32_t* d_scalars, size_t n,
+                     const int32_t* d_idx, typename G::Jacobian* out, float* acc_ms);
+// the first n points of a device vector as host affine points (the caller holds whatever orders the
+// vector's last writer before this blocking copy)
+template <class G>
+bh_status download_points(const bh_srs& v, size_t n, std::vector<typename G::Affine>* out);
 bh_status upload_fr(bh_ctx* ctx, const uint64_t* host, size_t n, size_t padded, uint32_t* dst);
 // the same through the context's pinned staging ring, enqueued on st (caller holds ctx->mu)
 bh_status upload_fr_staged(bh_ctx* ctx, const uint64_t* host, size_t n, size_t padded, uint32_t* dst, hipStream_t st);
@@ -475,7 +475,8 @@ bh_status srs_from_bytes(bh_ctx* ctx, int group, const uint8_t* bytes, size_t n,
 // reference-exact error semantics of multiexp (EOF / identity), host side
 bh_status multiexp_check(const bh_srs* bases, size_t base_offset, const uint64_t* density_words, size_t n,
                          const uint64_t* exps_canonical, bool need_exps);
-bh_status srs_upload_affine(bh_ctx* ctx, int group, const void* host_affine_g1_or_g2, size_t n, bh_srs* out);
+template <class T>
+bh_status srs_upload_affine(bh_ctx* ctx, const AffinePt<T>* pts, size_t n, bh_srs* out);
 // The all-to-all step of the distributed H pipeline: for each of nvec vectors of M = N*C
 // packed-Fr elements, chunk p of send goes to rank p, which stores it as chunk `this rank` of
 // recv; stream-ordered on st.  Over RCCL (comm.cpp) or, to run the identical prover code with N

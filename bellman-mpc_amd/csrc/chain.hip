@@ -225,17 +225,17 @@ void canonical_words(const Fr& x, uint32_t* w8) {
 // scalars (canonical, host) -> packed affine points in `out` (device) via the GPU
 template <class C, class T>
 bh_status fixed_base_to_srs(bh_ctx* ctx, const std::vector<AffinePt<T>>& table, const std::vector<Fr>& scalars,
-                            int group, bh_srs* out) {
+                            bh_srs* out) {
   const size_t n = scalars.size();
   out->ctx = ctx;
-  out->group = group;
+  out->group = HostOf<C>::ID;
   out->n = n;
   out->identity_idx.clear();
-  const int words = group == BH_G1 ? 24 : 48;
+  constexpr int words = HostOf<C>::WORDS;
   BH_TRY_HIP(out->pts.alloc(std::max<size_t>(n, 1) * words * 4));
   if (!n) return BH_OK;
   bh_srs tab;
-  bh_status s = srs_upload_affine(ctx, group, table.data(), table.size(), &tab);
+  bh_status s = srs_upload_affine(ctx, table.data(), table.size(), &tab);
   if (s) return s;
   const size_t chunk = std::min<size_t>(n, (size_t)1 << 21);
   DevBuf d_sc, d_xyzz, d_scr;
@@ -519,11 +519,11 @@ bh_status bh_chain_params(bh_ctx* ctx, size_t rounds, uint64_t seed, uint64_t al
   {
     std::lock_guard<std::mutex> lk(ctx->mu);
     BH_TRY_HIP(hipSetDevice(ctx->device));
-    if ((s = fixed_base_to_srs<G1Ops>(ctx, t1, hsc, BH_G1, &p->h))) return s;
-    if ((s = fixed_base_to_srs<G1Ops>(ctx, t1, l_sc, BH_G1, &p->l))) return s;
-    if ((s = fixed_base_to_srs<G1Ops>(ctx, t1, a_sc, BH_G1, &p->a))) return s;
-    if ((s = fixed_base_to_srs<G1Ops>(ctx, t1, b_sc, BH_G1, &p->b_g1))) return s;
-    if ((s = fixed_base_to_srs<G2Ops>(ctx, t2, b_sc, BH_G2, &p->b_g2))) return s;
+    if ((s = fixed_base_to_srs<G1Ops>(ctx, t1, hsc, &p->h))) return s;
+    if ((s = fixed_base_to_srs<G1Ops>(ctx, t1, l_sc, &p->l))) return s;
+    if ((s = fixed_base_to_srs<G1Ops>(ctx, t1, a_sc, &p->a))) return s;
+    if ((s = fixed_base_to_srs<G1Ops>(ctx, t1, b_sc, &p->b_g1))) return s;
+    if ((s = fixed_base_to_srs<G2Ops>(ctx, t2, b_sc, &p->b_g2))) return s;
   }
   // ic and the verifying key on the host (ni points)
   auto g1mul = [&](const Fr& k) { uint64_t c[4]; fr_to_canonical(k, c); return jac_to_affine(jac_mul(g1, c, 4)); };

@@ -10,18 +10,12 @@
 //   k_normalize  : XYZZ -> affine with one inversion per CHUNK points (Montgomery's
 //                  trick), result packed canonical in the bh_srs layout.
 #include "crs.h"
+#include "group_host.h"  // FieldOf
 #include "msm.h"  // G1_TABLE_REC
 
 #include <algorithm>
 
 namespace bh {
-
-template <class C>
-struct FieldOf;
-template <>
-struct FieldOf<G1Ops> { using F = G1F; };
-template <>
-struct FieldOf<G2Ops> { using F = Fp2Ops; };
 
 template <class C>
 __device__ __forceinline__ typename C::A load_affine_packed(const uint32_t* base, size_t i) {

@@ -5,6 +5,7 @@
 // Proof::write / Parameters::write (groth16/mod.rs:42-48, 260-290).
 // 64-bit limbs, Montgomery R = 2^384 (Fp) / 2^256 (Fr) -- the bls12_381 layout.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 #include "constants.h"
@@ -320,59 +321,7 @@ static inline Jac<T> xyzz_to_jac(const T& X, const T& Y, const T& ZZ, const T& Z
   return r;
 }
 
-// ------------------------------------------------------------ conversions / encodings
-// Device packed words (12 x u32 per Fp, value = x * 2^406 mod p, canonical) -> host Montgomery
-static inline Fp fp_from_dev_words(const uint32_t* w) {
-  Fp a;
-  for (int i = 0; i < 6; i++) a.v[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
-  // a = x*2^406 (raw); host Montgomery of x = a * 2^-22 = mont_mul(a, 2^362 mod p)
-  static Fp K = [] {
-    uint64_t two[6] = {2, 0, 0, 0, 0, 0};
-    Fp t = from_int<6>(two);
-    uint64_t e[1] = {362};
-    Fp k = pow_vartime(t, e, 1);  // Montgomery(2^362)
-    uint64_t raw[6];
-    to_int(k, raw);               // canonical 2^362 mod p
-    Fp out; memcpy(out.v, raw, sizeof raw);
-    return out;
-  }();
-  return mul(a, K);
-}
-// Device packed words of a field whose device Montgomery radix is 2^rlog (G1's form, R = 2^(N*BITS)
-// of its limb configuration: 2^390 for the balanced 13 x 30-bit digits) -> host Montgomery:
-// a * 2^-(rlog - 384) = mont_mul(a, 2^(768 - rlog) mod p)
-template <int RLOG>
-static inline Fp fp_from_dev_words_r(const uint32_t* w) {
-  Fp a;
-  for (int i = 0; i < 6; i++) a.v[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
-  static Fp K = [] {
-    uint64_t two[6] = {2, 0, 0, 0, 0, 0};
-    Fp t = from_int<6>(two);
-    uint64_t e[1] = {768 - RLOG};
-    Fp k = pow_vartime(t, e, 1);  // Montgomery(2^(768 - RLOG))
-    uint64_t raw[6];
-    to_int(k, raw);               // canonical
-    Fp out; memcpy(out.v, raw, sizeof raw);
-    return out;
-  }();
-  return mul(a, K);
-}
-// host Montgomery -> device packed words (x * 2^406 mod p)
-static inline void fp_to_dev_words(const Fp& x, uint32_t* w) {
-  static Fp K = [] {
-    uint64_t two[6] = {2, 0, 0, 0, 0, 0};
-    Fp t = from_int<6>(two);
-    uint64_t e[1] = {406};
-    Fp k = pow_vartime(t, e, 1);
-    uint64_t raw[6];
-    to_int(k, raw);
-    Fp out; memcpy(out.v, raw, sizeof raw);
-    return out;
-  }();
-  Fp d = mul(x, K);  // x*2^384 * 2^406 * 2^-384 = x*2^406 (as raw value)
-  for (int i = 0; i < 6; i++) { w[2 * i] = (uint32_t)d.v[i]; w[2 * i + 1] = (uint32_t)(d.v[i] >> 32); }
-}
-
+// ------------------------------------------------------------ encodings
 static inline void fp_to_be(const Fp& a, uint8_t* out48) {
   uint64_t raw[6];
   to_int(a, raw);
@@ -405,31 +354,41 @@ static inline bool fp_lex_largest(const Fp& a) {
   return false;
 }
 
-static inline void g1_to_compressed(const AffinePt<Fp>& a, uint8_t* out48) {
-  if (a.infinity) { memset(out48, 0, 48); out48[0] = 0xC0; return; }
-  fp_to_be(a.x, out48);
-  out48[0] |= 0x80;
-  if (fp_lex_largest(a.y)) out48[0] |= 0x20;
+static inline bool lex_largest(const Fp& y) { return fp_lex_largest(y); }
+static inline bool lex_largest(const Fp2& y) {
+  return fp_lex_largest(y.c1) || (y.c1.is_zero() && fp_lex_largest(y.c0));
 }
-static inline void g1_to_uncompressed(const AffinePt<Fp>& a, uint8_t* out96) {
-  if (a.infinity) { memset(out96, 0, 96); out96[0] = 0x40; return; }
-  fp_to_be(a.x, out96);
-  fp_to_be(a.y, out96 + 48);
+
+// A point's Fp components in memory order: x, y over Fp; x.c0, x.c1, y.c0, y.c1 over Fp2 (the
+// order of the packed device layout, group_host.h).  On the wire (zcash) every component is 48
+// big-endian bytes, c1 before c0: wire slot k holds component wire_component<T>(k), and the three
+// flag bits (compressed, infinity, sort) sit on top of slot 0.
+template <class T>
+constexpr int COMPONENTS = 2 * sizeof(T) / sizeof(Fp);
+template <class T>
+static inline const Fp* components(const AffinePt<T>& a) {
+  static_assert(sizeof(T) % sizeof(Fp) == 0 && offsetof(AffinePt<T>, y) == sizeof(T), "x, y are packed Fp arrays");
+  return reinterpret_cast<const Fp*>(&a);
 }
-static inline void g2_to_compressed(const AffinePt<Fp2>& a, uint8_t* out96) {
-  if (a.infinity) { memset(out96, 0, 96); out96[0] = 0xC0; return; }
-  fp_to_be(a.x.c1, out96);
-  fp_to_be(a.x.c0, out96 + 48);
-  out96[0] |= 0x80;
-  bool lex = fp_lex_largest(a.y.c1) || (a.y.c1.is_zero() && fp_lex_largest(a.y.c0));
-  if (lex) out96[0] |= 0x20;
+template <class T>
+static inline Fp* components(AffinePt<T>& a) { return const_cast<Fp*>(components(const_cast<const AffinePt<T>&>(a))); }
+template <class T>
+constexpr int wire_component(int k) { return sizeof(T) == sizeof(Fp) ? k : (k ^ 1); }
+
+// the x coordinate with the compression and sort flags
+template <class T>
+static inline void to_compressed(const AffinePt<T>& a, uint8_t* out) {
+  constexpr int N = COMPONENTS<T> / 2;
+  if (a.infinity) { memset(out, 0, 48 * N); out[0] = 0xC0; return; }
+  for (int k = 0; k < N; k++) fp_to_be(components(a)[wire_component<T>(k)], out + 48 * k);
+  out[0] |= 0x80;
+  if (lex_largest(a.y)) out[0] |= 0x20;
 }
-static inline void g2_to_uncompressed(const AffinePt<Fp2>& a, uint8_t* out192) {
-  if (a.infinity) { memset(out192, 0, 192); out192[0] = 0x40; return; }
-  fp_to_be(a.x.c1, out192);
-  fp_to_be(a.x.c0, out192 + 48);
-  fp_to_be(a.y.c1, out192 + 96);
-  fp_to_be(a.y.c0, out192 + 144);
+template <class T>
+static inline void to_uncompressed(const AffinePt<T>& a, uint8_t* out) {
+  constexpr int N = COMPONENTS<T>;
+  if (a.infinity) { memset(out, 0, 48 * N); out[0] = 0x40; return; }
+  for (int k = 0; k < N; k++) fp_to_be(components(a)[wire_component<T>(k)], out + 48 * k);
 }
 
 template <class T>
@@ -446,46 +405,26 @@ static inline bool in_subgroup(const AffinePt<T>& p) {
   return p.infinity || jac_is_identity(jac_mul(jac_from_affine(p), R, 4));
 }
 
-// G1Affine::from_uncompressed_unchecked semantics (+ on-curve check when check_curve,
+// G1Affine/G2Affine::from_uncompressed_unchecked semantics (+ on-curve check when check_curve,
 // + subgroup check when check_subgroup); returns 0 ok, -1 invalid encoding, -2 not on
 // curve, -3 not in the subgroup
-static inline int g1_from_uncompressed(const uint8_t* in96, AffinePt<Fp>* out, bool check_curve,
-                                       bool check_subgroup = false) {
-  uint8_t flags = in96[0] >> 5;
+template <class T>
+static inline int from_uncompressed(const uint8_t* in, AffinePt<T>* out, bool check_curve,
+                                    bool check_subgroup = false) {
+  constexpr int N = COMPONENTS<T>;
+  uint8_t flags = in[0] >> 5;
   if (flags & 0x4) return -1;  // compression flag set
   if (flags & 0x1) return -1;  // sort flag set
   if (flags & 0x2) {           // infinity
-    for (int i = 0; i < 96; i++) {
-      uint8_t b = (i == 0) ? (in96[0] & 0x1F) : in96[i];
+    for (int i = 0; i < 48 * N; i++) {
+      uint8_t b = (i == 0) ? (in[0] & 0x1F) : in[i];
       if (b) return -1;
     }
-    out->infinity = true; out->x = Fp::zero(); out->y = Fp::zero();
+    out->infinity = true; out->x = tzero<T>(); out->y = tzero<T>();
     return 0;
   }
-  if (!fp_from_be(in96, &out->x, 0xE0)) return -1;
-  if (!fp_from_be(in96 + 48, &out->y)) return -1;
-  out->infinity = false;
-  if (check_curve && !on_curve(*out)) return -2;
-  if (check_subgroup && !in_subgroup(*out)) return -3;
-  return 0;
-}
-static inline int g2_from_uncompressed(const uint8_t* in192, AffinePt<Fp2>* out, bool check_curve,
-                                       bool check_subgroup = false) {
-  uint8_t flags = in192[0] >> 5;
-  if (flags & 0x4) return -1;
-  if (flags & 0x1) return -1;
-  if (flags & 0x2) {
-    for (int i = 0; i < 192; i++) {
-      uint8_t b = (i == 0) ? (in192[0] & 0x1F) : in192[i];
-      if (b) return -1;
-    }
-    out->infinity = true; out->x = Fp2::zero(); out->y = Fp2::zero();
-    return 0;
-  }
-  if (!fp_from_be(in192, &out->x.c1, 0xE0)) return -1;
-  if (!fp_from_be(in192 + 48, &out->x.c0)) return -1;
-  if (!fp_from_be(in192 + 96, &out->y.c1)) return -1;
-  if (!fp_from_be(in192 + 144, &out->y.c0)) return -1;
+  for (int k = 0; k < N; k++)
+    if (!fp_from_be(in + 48 * k, &components(*out)[wire_component<T>(k)], k == 0 ? 0xE0 : 0)) return -1;
   out->infinity = false;
   if (check_curve && !on_curve(*out)) return -2;
   if (check_subgroup && !in_subgroup(*out)) return -3;

@@ -53,6 +53,9 @@ struct bh_job {
 
 namespace {
 
+MsmWorkspace<G1Ops>& slot_ws(bh_job_slot* sl, G1Host) { return sl->ws1; }
+MsmWorkspace<G2Ops>& slot_ws(bh_job_slot* sl, G2Host) { return sl->ws2; }
+
 // The shape of a multiexp for slot reuse: a slot whose buffers were sized by the same kind of
 // job (same bases, offset, length) needs no reallocation -- and a reallocation is a hipFree, which
 // waits for the whole device (the submit would block behind every multiexp in flight).
@@ -151,8 +154,10 @@ bh_status enqueue_msm(bh_ctx* ctx, bh_job* job, MsmWorkspace<C>& ws, const bh_sr
           r.pre != job->sh.pre || r.slot->use != r.use || r.slot == sl)
         continue;
       const uint32_t *e, *cn, *of;
-      if (r.group == BH_G1) { e = r.slot->ws1.entries; cn = r.slot->ws1.counts; of = r.slot->ws1.offsets; }
-      else { e = r.slot->ws2.entries; cn = r.slot->ws2.counts; of = r.slot->ws2.offsets; }
+      with_group(r.group, [&](auto g) {
+        const auto& src = slot_ws(r.slot, g);
+        e = src.entries; cn = src.counts; of = src.offsets;
+      });
       BH_TRY_HIP(ws.reserve_shape(n, job->sh));
       const size_t nbt = (size_t)job->sh.Wb * job->sh.NB;
       // stream order on the sort stream: after the source's sort, before any later reuse of it
@@ -192,8 +197,10 @@ bh_status enqueue_msm(bh_ctx* ctx, bh_job* job, MsmWorkspace<C>& ws, const bh_sr
             r.NB != job->sh.NB || r.Wb != job->sh.Wb || r.pre != job->sh.pre || r.slot->use != r.use || r.slot == sl)
           continue;
         const uint32_t *e, *of;
-        if (r.group == BH_G1) { e = r.slot->ws1.entries; of = r.slot->ws1.offsets; }
-        else { e = r.slot->ws2.entries; of = r.slot->ws2.offsets; }
+        with_group(r.group, [&](auto g) {
+          const auto& src = slot_ws(r.slot, g);
+          e = src.entries; of = src.offsets;
+        });
         BH_TRY_HIP(ws.reserve_shape(n, job->sh));
         const size_t nbt = (size_t)job->sh.Wb * job->sh.NB, Emax = n * (size_t)job->sh.W;
         BH_TRY_HIP(sl->dscan2.alloc(derive_scratch_words(Emax) * 4));
@@ -278,11 +285,10 @@ bh_status enqueue_job(bh_ctx* ctx, bh_job* job, const bh_srs* bases, size_t base
   const size_t set = density_set(density_words, n);
   // window tables as the prover uses them: not under a forced window size (bh_ctx_set_window)
   const bool tables = ctx->tables && !job->window_override;
-  bh_status s = bases->group == BH_G1
-                    ? enqueue_msm<G1Ops>(ctx, job, sl->ws1, bases, base_offset, n, set, density_words, d_scalars,
-                                         tables, js)
-                    : enqueue_msm<G2Ops>(ctx, job, sl->ws2, bases, base_offset, n, set, density_words, d_scalars,
-                                         tables, js);
+  bh_status s = with_group(bases->group, [&](auto g) {
+    return enqueue_msm<typename decltype(g)::Ops>(ctx, job, slot_ws(sl, g), bases, base_offset, n, set, density_words,
+                                                  d_scalars, tables, js);
+  });
   if (s) return fail(s);
   return BH_OK;
 }
@@ -469,8 +475,9 @@ bh_status bh_multiexp_wait(bh_job* job, uint8_t* out) {
   if (j->empty) {
     if (j->status) return j->status;
     if (!out) return BH_ERR_INVALID_ARGUMENT;
-    if (j->group == BH_G1) g1_to_uncompressed(jac_to_affine(jac_identity<Fp>()), out);
-    else g2_to_uncompressed(jac_to_affine(jac_identity<bh::Fp2>()), out);
+    with_group(j->group, [&](auto g) {
+      to_uncompressed(jac_to_affine(jac_identity<typename decltype(g)::Field>()), out);
+    });
     return BH_OK;
   }
   if (!sl) return BH_ERR_INVALID_ARGUMENT;  // its context was destroyed: no result exists
@@ -478,8 +485,9 @@ bh_status bh_multiexp_wait(bh_job* job, uint8_t* out) {
   const hipError_t e = hipEventSynchronize(sl->done);  // Waiter::wait: a host-side event sync
   bh_status s = e == hipSuccess ? BH_OK : BH_ERR_HIP;
   if (!s && out) {
-    if (j->group == BH_G1) g1_to_uncompressed(jac_to_affine(combine_g1(sl->ws1.host_window_sums, j->sh)), out);
-    else g2_to_uncompressed(jac_to_affine(combine_g2(sl->ws2.host_window_sums, j->sh)), out);
+    with_group(j->group, [&](auto g) {
+      to_uncompressed(jac_to_affine(combine<decltype(g)>(slot_ws(sl, g).host_window_sums, j->sh)), out);
+    });
   }
   give_slot(*j->reg, sl);
   if (!out && !s) return BH_ERR_INVALID_ARGUMENT;

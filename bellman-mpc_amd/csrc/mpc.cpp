@@ -57,6 +57,11 @@ namespace {
 
 AffinePt<Fp> g1_gen() { return jac_to_affine(crs_g1_gen()); }
 AffinePt<Fp2> g2_gen() { return jac_to_affine(crs_g2_gen()); }
+// device vector -> host affine points (caller holds ctx->mu; the stream is idle)
+template <class T>
+bh_status download(const bh_srs* s, std::vector<AffinePt<T>>* out) {
+  return download_points<HostOfField<T>>(*s, s->n, out);
+}
 template <class T>
 AffinePt<T> pt_mul(const AffinePt<T>& p, const uint64_t k[4]) {
   return jac_to_affine(jac_mul(jac_from_affine(p), k, 4));
@@ -66,36 +71,13 @@ AffinePt<T> pt_neg(AffinePt<T> p) {
   if (!p.infinity) p.y = neg(p.y);
   return p;
 }
-// device vector -> host affine points (caller holds ctx->mu; the stream is idle)
-bh_status download_g1(const bh_srs* s, std::vector<AffinePt<Fp>>* out) {
-  std::vector<uint32_t> w(s->n * 24);
-  if (s->n) BH_TRY_HIP(hipMemcpy(w.data(), s->pts.p, s->n * 96, hipMemcpyDeviceToHost));
-  out->resize(s->n);
-  for (size_t i = 0; i < s->n; i++)
-    (*out)[i] = AffinePt<Fp>{fp_from_dev_words_g1(&w[i * 24]), fp_from_dev_words_g1(&w[i * 24 + 12]), false};
-  for (size_t i : s->identity_idx) (*out)[i].infinity = true;
-  return BH_OK;
-}
-bh_status download_g2(const bh_srs* s, std::vector<AffinePt<Fp2>>* out) {
-  std::vector<uint32_t> w(s->n * 48);
-  if (s->n) BH_TRY_HIP(hipMemcpy(w.data(), s->pts.p, s->n * 192, hipMemcpyDeviceToHost));
-  out->resize(s->n);
-  for (size_t i = 0; i < s->n; i++) {
-    const uint32_t* p = &w[i * 48];
-    (*out)[i] = AffinePt<Fp2>{Fp2{fp_from_dev_words(p), fp_from_dev_words(p + 12)},
-                              Fp2{fp_from_dev_words(p + 24), fp_from_dev_words(p + 36)}, false};
-  }
-  for (size_t i : s->identity_idx) (*out)[i].infinity = true;
-  return BH_OK;
-}
-
 bh_status clone_srs(bh_ctx* ctx, const bh_srs* in, std::unique_ptr<bh_srs>* out) {
   std::unique_ptr<bh_srs> r(new bh_srs());
   r->ctx = ctx;
   r->group = in->group;
   r->n = in->n;
   r->identity_idx = in->identity_idx;
-  const size_t bytes = in->n * (in->group == BH_G1 ? 96 : 192);
+  const size_t bytes = in->n * with_group(in->group, [](auto g) { return decltype(g)::WORDS * (size_t)4; });
   BH_TRY_HIP(r->pts.alloc(std::max<size_t>(bytes, 16)));
   if (bytes) {
     BH_TRY_HIP(hipMemcpyAsync(r->pts.p, in->pts.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
@@ -113,9 +95,9 @@ struct Tables {
   bh_status upload(bh_ctx* ctx) {
     const auto a = crs_table_g1();
     const auto b = crs_table_g2();
-    bh_status s = srs_upload_affine(ctx, BH_G1, a.data(), a.size(), &t1);
+    bh_status s = srs_upload_affine(ctx, a.data(), a.size(), &t1);
     if (s) return s;
-    return srs_upload_affine(ctx, BH_G2, b.data(), b.size(), &t2);
+    return srs_upload_affine(ctx, b.data(), b.size(), &t2);
   }
 };
 
@@ -140,8 +122,8 @@ bh_status new_tau_pair(bh_ctx* ctx, const Tables& tab, const MpcStorage* st, int
   }
   if ((s = varbase_mul(ctx, g1, d_sc.as<uint32_t>(), stride, 255, c->res[2 * j].get()))) return s;
   if ((s = varbase_mul(ctx, g2, d_sc.as<uint32_t>(), stride, 255, c->res[2 * j + 1].get()))) return s;
-  if ((s = fixed_base_device<G1Ops>(ctx, tab.t1, d_sc.as<uint32_t>(), g1->n, BH_G1, c->mine[2 * j].get()))) return s;
-  return fixed_base_device<G2Ops>(ctx, tab.t2, d_sc.as<uint32_t>(), g1->n, BH_G2, c->mine[2 * j + 1].get());
+  if ((s = fixed_base_device<G1Ops>(ctx, tab.t1, d_sc.as<uint32_t>(), g1->n, c->mine[2 * j].get()))) return s;
+  return fixed_base_device<G2Ops>(ctx, tab.t2, d_sc.as<uint32_t>(), g1->n, c->mine[2 * j + 1].get());
 }
 
 // to_storage_format (mpc.rs:381-394, 910-923)
@@ -168,15 +150,10 @@ bool verify_pair(const HostPair& p, const AffinePt<Fp>& o1) {
   return pairing_product_is_one({{p.r1, ng2}, {o1, p.m2}}) && pairing_product_is_one({{p.r1, ng2}, {g1_gen(), p.r2}});
 }
 
-bh_status msm_g1(bh_ctx* ctx, const bh_srs* b, const uint32_t* d_z, AffinePt<Fp>* out) {
-  Jac<Fp> r;
-  bh_status s = msm_g1_device(ctx, b, 0, d_z, b->n, nullptr, &r, nullptr);
-  if (!s) *out = jac_to_affine(r);
-  return s;
-}
-bh_status msm_g2(bh_ctx* ctx, const bh_srs* b, const uint32_t* d_z, AffinePt<Fp2>* out) {
-  Jac<Fp2> r;
-  bh_status s = msm_g2_device(ctx, b, 0, d_z, b->n, nullptr, &r, nullptr);
+template <class T>
+bh_status msm(bh_ctx* ctx, const bh_srs* b, const uint32_t* d_z, AffinePt<T>* out) {
+  Jac<T> r;
+  bh_status s = msm_device<HostOfField<T>>(ctx, b, 0, d_z, b->n, nullptr, &r, nullptr);
   if (!s) *out = jac_to_affine(r);
   return s;
 }
@@ -208,15 +185,15 @@ bh_status verify_tau_pair(bh_ctx* ctx, const MpcStorage* st, const MpcContrib* c
                           int nbits, bool* ok, double* miller_ms) {
   AffinePt<Fp> s1;
   AffinePt<Fp2> s2;
-  bh_status s = msm_g1(ctx, c->res[2 * j].get(), d_z, &s1);
+  bh_status s = msm(ctx, c->res[2 * j].get(), d_z, &s1);
   if (s) return s;
-  if ((s = msm_g2(ctx, c->res[2 * j + 1].get(), d_z, &s2))) return s;
+  if ((s = msm(ctx, c->res[2 * j + 1].get(), d_z, &s2))) return s;
   bh_srs q;
   if ((s = varbase_mul(ctx, st->v[2 * j].get(), d_z, 8, nbits, &q))) return s;
   std::vector<AffinePt<Fp>> qh;
   std::vector<AffinePt<Fp2>> m2;
-  if ((s = download_g1(&q, &qh))) return s;
-  if ((s = download_g2(c->mine[2 * j + 1].get(), &m2))) return s;
+  if ((s = download(&q, &qh))) return s;
+  if ((s = download(c->mine[2 * j + 1].get(), &m2))) return s;
   const AffinePt<Fp2> g2 = g2_gen(), ng2 = pt_neg(g2);
   const auto t0 = std::chrono::steady_clock::now();
   Fp12 f = pooled_miller(ctx, qh, m2);
@@ -243,28 +220,19 @@ void put_u32(std::vector<uint8_t>& v, size_t n) {
   v.push_back((uint8_t)(n >> 8));
   v.push_back((uint8_t)n);
 }
-void put_g1(std::vector<uint8_t>& v, const AffinePt<Fp>& p) {
-  uint8_t b[96];
-  g1_to_uncompressed(p, b);
-  v.insert(v.end(), b, b + 96);
-}
-void put_g2(std::vector<uint8_t>& v, const AffinePt<Fp2>& p) {
-  uint8_t b[192];
-  g2_to_uncompressed(p, b);
-  v.insert(v.end(), b, b + 192);
+template <class T>
+void put(std::vector<uint8_t>& v, const AffinePt<T>& p) {
+  uint8_t b[HostOfField<T>::WIRE];
+  to_uncompressed(p, b);
+  v.insert(v.end(), b, b + sizeof b);
 }
 bh_status put_vec(std::vector<uint8_t>& v, const bh_srs* s) {
-  bh_status st;
-  if (s->group == BH_G1) {
-    std::vector<AffinePt<Fp>> h;
-    if ((st = download_g1(s, &h))) return st;
-    for (const auto& p : h) put_g1(v, p);
-  } else {
-    std::vector<AffinePt<Fp2>> h;
-    if ((st = download_g2(s, &h))) return st;
-    for (const auto& p : h) put_g2(v, p);
-  }
-  return BH_OK;
+  return with_group(s->group, [&](auto g) {
+    std::vector<typename decltype(g)::Affine> h;
+    const bh_status st = download(s, &h);
+    for (const auto& p : h) put(v, p);
+    return st;
+  });
 }
 
 struct Reader {
@@ -277,25 +245,19 @@ struct Reader {
     o += 4;
     return BH_OK;
   }
-  bh_status g1(AffinePt<Fp>* p) {
-    if (len - o < 96) return BH_ERR_UNEXPECTED_EOF;
-    const int r = g1_from_uncompressed(in + o, p, checked != 0, checked != 0);
-    o += 96;
-    if (r == -3) return BH_ERR_NOT_IN_SUBGROUP;
-    if (r == -2) return BH_ERR_NOT_ON_CURVE;
-    return (r || p->infinity) ? BH_ERR_INVALID_ENCODING : BH_OK;
-  }
-  bh_status g2(AffinePt<Fp2>* p) {
-    if (len - o < 192) return BH_ERR_UNEXPECTED_EOF;
-    const int r = g2_from_uncompressed(in + o, p, checked != 0, checked != 0);
-    o += 192;
+  template <class T>
+  bh_status point(AffinePt<T>* p) {
+    constexpr size_t pb = HostOfField<T>::WIRE;
+    if (len - o < pb) return BH_ERR_UNEXPECTED_EOF;
+    const int r = from_uncompressed(in + o, p, checked != 0, checked != 0);
+    o += pb;
     if (r == -3) return BH_ERR_NOT_IN_SUBGROUP;
     if (r == -2) return BH_ERR_NOT_ON_CURVE;
     return (r || p->infinity) ? BH_ERR_INVALID_ENCODING : BH_OK;
   }
   // n consecutive points of one group -> device vector (the checks of bh_params_load)
   bh_status vec(bh_ctx* ctx, int group, size_t n, std::unique_ptr<bh_srs>* out) {
-    const size_t pb = group == BH_G1 ? 96 : 192;
+    const size_t pb = with_group(group, [](auto g) { return decltype(g)::WIRE; });
     if (n > (len - o) / pb) return BH_ERR_UNEXPECTED_EOF;
     out->reset(new bh_srs());
     const bh_status s = srs_from_bytes(ctx, group, in + o, n, checked, true, out->get());
@@ -309,8 +271,8 @@ struct Reader {
 bh_status storage_write(const MpcStorage* st, bool common, std::vector<uint8_t>& v) {
   if (common) put_u32(v, st->v[0]->n);
   for (int k = 0; k < 2; k++) {
-    put_g1(v, st->p1[k]);
-    put_g2(v, st->p2[k]);
+    put(v, st->p1[k]);
+    put(v, st->p2[k]);
   }
   for (int k = 0; k < 6; k++) {
     if (!common) put_u32(v, st->v[k]->n);
@@ -329,7 +291,7 @@ bh_status storage_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checke
   size_t n = 0;
   if (common && (s = r.u32(&n))) return s;
   for (int k = 0; k < 2; k++) {
-    if ((s = r.g1(&st->p1[k])) || (s = r.g2(&st->p2[k]))) return s;
+    if ((s = r.point(&st->p1[k])) || (s = r.point(&st->p2[k]))) return s;
   }
   for (int k = 0; k < 6; k++) {
     if (!common) {
@@ -354,24 +316,24 @@ bh_status storage_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checke
 bh_status contrib_write(const MpcContrib* c, bool common, std::vector<uint8_t>& v) {
   for (int k = 0; k < 2; k++) {
     const HostPair& p = c->pp[common ? k : 1 - k];
-    put_g1(v, p.r1);
-    put_g2(v, p.r2);
-    put_g1(v, p.m1);
-    put_g2(v, p.m2);
+    put(v, p.r1);
+    put(v, p.r2);
+    put(v, p.m1);
+    put(v, p.m2);
   }
   for (int j = 0; j < 3; j++) {
     std::vector<AffinePt<Fp>> r1, m1;
     std::vector<AffinePt<Fp2>> r2, m2;
     bh_status s;
-    if ((s = download_g1(c->res[2 * j].get(), &r1)) || (s = download_g2(c->res[2 * j + 1].get(), &r2)) ||
-        (s = download_g1(c->mine[2 * j].get(), &m1)) || (s = download_g2(c->mine[2 * j + 1].get(), &m2)))
+    if ((s = download(c->res[2 * j].get(), &r1)) || (s = download(c->res[2 * j + 1].get(), &r2)) ||
+        (s = download(c->mine[2 * j].get(), &m1)) || (s = download(c->mine[2 * j + 1].get(), &m2)))
       return s;
     put_u32(v, r1.size());
     for (size_t i = 0; i < r1.size(); i++) {
-      put_g1(v, r1[i]);
-      put_g2(v, r2[i]);
-      put_g1(v, m1[i]);
-      put_g2(v, m2[i]);
+      put(v, r1[i]);
+      put(v, r2[i]);
+      put(v, m1[i]);
+      put(v, m2[i]);
     }
   }
   return BH_OK;
@@ -385,25 +347,26 @@ bh_status contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checke
   bh_status s;
   for (int k = 0; k < 2; k++) {
     HostPair& p = c->pp[common ? k : 1 - k];
-    if ((s = r.g1(&p.r1)) || (s = r.g2(&p.r2)) || (s = r.g1(&p.m1)) || (s = r.g2(&p.m2))) return s;
+    if ((s = r.point(&p.r1)) || (s = r.point(&p.r2)) || (s = r.point(&p.m1)) || (s = r.point(&p.m2))) return s;
   }
   for (int j = 0; j < 3; j++) {
     size_t n;
     if ((s = r.u32(&n))) return s;
-    if (n > (len - r.o) / 576) return BH_ERR_UNEXPECTED_EOF;
+    const size_t w[4] = {G1Host::WIRE, G2Host::WIRE, G1Host::WIRE, G2Host::WIRE};
+    const size_t pair = w[0] + w[1] + w[2] + w[3];
+    if (n > (len - r.o) / pair) return BH_ERR_UNEXPECTED_EOF;
     // de-interleave the list into its four vectors
     std::vector<uint8_t> col[4];
-    const size_t w[4] = {96, 192, 96, 192};
     for (int k = 0; k < 4; k++) col[k].resize(n * w[k]);
     for (size_t i = 0; i < n; i++) {
-      const uint8_t* b = bytes + r.o + i * 576;
+      const uint8_t* b = bytes + r.o + i * pair;
       size_t off = 0;
       for (int k = 0; k < 4; k++) {
         memcpy(&col[k][i * w[k]], b + off, w[k]);
         off += w[k];
       }
     }
-    r.o += n * 576;
+    r.o += n * pair;
     std::unique_ptr<bh_srs>* dst[4] = {&c->res[2 * j], &c->res[2 * j + 1], &c->mine[2 * j], &c->mine[2 * j + 1]};
     for (int k = 0; k < 4; k++) {
       dst[k]->reset(new bh_srs());
@@ -426,19 +389,19 @@ bh_status emit(const std::vector<uint8_t>& v, uint8_t* out, size_t cap, size_t* 
 bh_status storage_point(const MpcStorage* st, int which, uint8_t* out) {
   if (!st || !out || which < 0 || which > 3) return BH_ERR_INVALID_ARGUMENT;
   if (which & 1)
-    g2_to_uncompressed(st->p2[which >> 1], out);
+    to_uncompressed(st->p2[which >> 1], out);
   else
-    g1_to_uncompressed(st->p1[which >> 1], out);
+    to_uncompressed(st->p1[which >> 1], out);
   return BH_OK;
 }
 bh_status contrib_point(const MpcContrib* c, int which, uint8_t* out) {
   if (!c || !out || which < 0 || which > 7) return BH_ERR_INVALID_ARGUMENT;
   const HostPair& p = c->pp[which >> 2];
   switch (which & 3) {
-    case 0: g1_to_uncompressed(p.r1, out); break;
-    case 1: g2_to_uncompressed(p.r2, out); break;
-    case 2: g1_to_uncompressed(p.m1, out); break;
-    default: g2_to_uncompressed(p.m2, out); break;
+    case 0: to_uncompressed(p.r1, out); break;
+    case 1: to_uncompressed(p.r2, out); break;
+    case 2: to_uncompressed(p.m1, out); break;
+    default: to_uncompressed(p.m2, out); break;
   }
   return BH_OK;
 }
@@ -486,8 +449,8 @@ bh_status bh_mpc_common_initial(bh_ctx* ctx, size_t len, bh_mpc_common** out) {
   bh_status s;
   st->v[0].reset(new bh_srs());
   st->v[1].reset(new bh_srs());
-  if ((s = srs_upload_affine(ctx, BH_G1, v1.data(), len, st->v[0].get()))) return s;
-  if ((s = srs_upload_affine(ctx, BH_G2, v2.data(), len, st->v[1].get()))) return s;
+  if ((s = srs_upload_affine(ctx, v1.data(), len, st->v[0].get()))) return s;
+  if ((s = srs_upload_affine(ctx, v2.data(), len, st->v[1].get()))) return s;
   for (int k = 2; k < 6; k++)
     if ((s = clone_srs(ctx, st->v[k & 1].get(), &st->v[k]))) return s;
   *out = st.release();
@@ -679,8 +642,8 @@ bh_status bh_mpc_uncommon_verify(bh_ctx* ctx, const bh_mpc_uncommon* matrix, con
   for (int j = 0; j < 3 && ok; j++) {
     // e(sum z_i new_i, gamma_or_delta_g2) == e(sum z_i matrix_i, G2)
     AffinePt<Fp> sn, sm;
-    if ((s = msm_g1(ctx, c->res[2 * j].get(), d_z.as<uint32_t>(), &sn))) return s;
-    if ((s = msm_g1(ctx, matrix->v[2 * j].get(), d_z.as<uint32_t>(), &sm))) return s;
+    if ((s = msm(ctx, c->res[2 * j].get(), d_z.as<uint32_t>(), &sn))) return s;
+    if ((s = msm(ctx, matrix->v[2 * j].get(), d_z.as<uint32_t>(), &sm))) return s;
     ok = pairing_product_is_one({{sn, c->pp[j == 0 ? 0 : 1].r2}, {sm, ng2}});
   }
   if (!ok) return BH_OK;

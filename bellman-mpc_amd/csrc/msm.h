@@ -65,7 +65,7 @@ inline size_t reduce_partial_points(const MsmShape& sh, bool g2) {
   return (size_t)sh.Wb * (g.col_points > g.row_points ? g.col_points : g.row_points);
 }
 // A bucket shard's device result is out[0] + 2^reduce_split_shift * out[1] + bk_lo * out[2]
-// (combine_g1 / combine_g2; out[2] = the plain sum of the range's buckets, each of which holds
+// (combine<G>, api.hip; out[2] = the plain sum of the range's buckets, each of which holds
 // digit bk_lo more than its position in the range).
 struct MsmTiming {
   hipEvent_t ev_acc_begin = nullptr, ev_acc_end = nullptr;  // bracket k_accumulate_dev

@@ -36,24 +36,19 @@ struct Reader {
 };
 
 // VerifyingKey::read uses from_uncompressed (checked), groth16/mod.rs:161-222
-bh_status read_g1_vk(Reader& r, AffinePt<Fp>* out, bool reject_identity) {
+template <class T>
+bh_status read_vk_point(Reader& r, AffinePt<T>* out, bool reject_identity) {
   const uint8_t* b;
-  if (!r.take(96, &b)) return BH_ERR_INVALID_ENCODING;
-  if (g1_from_uncompressed(b, out, true, true) != 0) return BH_ERR_INVALID_ENCODING;
+  if (!r.take(HostOfField<T>::WIRE, &b)) return BH_ERR_INVALID_ENCODING;
+  if (from_uncompressed(b, out, true, true) != 0) return BH_ERR_INVALID_ENCODING;
   if (reject_identity && out->infinity) return BH_ERR_INVALID_ENCODING;
-  return BH_OK;
-}
-bh_status read_g2_vk(Reader& r, AffinePt<bh::Fp2>* out) {
-  const uint8_t* b;
-  if (!r.take(192, &b)) return BH_ERR_INVALID_ENCODING;
-  if (g2_from_uncompressed(b, out, true, true) != 0) return BH_ERR_INVALID_ENCODING;
   return BH_OK;
 }
 
 bh_status read_vec(bh_ctx* ctx, Reader& r, int group, int checked, bh_srs* out) {
   uint32_t len;
   if (!r.u32be(&len)) return BH_ERR_INVALID_ENCODING;
-  const size_t pb = group == BH_G1 ? 96 : 192;
+  const size_t pb = with_group(group, [](auto g) { return decltype(g)::WIRE; });
   const uint8_t* b;
   if (!r.take((size_t)len * pb, &b)) return BH_ERR_INVALID_ENCODING;
   // Parameters::read rejects points at infinity in every vector (mod.rs:309-318)
@@ -62,30 +57,36 @@ bh_status read_vec(bh_ctx* ctx, Reader& r, int group, int checked, bh_srs* out) 
   return s;
 }
 
-void write_vec(const bh_srs& v, std::vector<uint8_t>& out) {
-  const size_t n = v.n;
+void put_u32be(std::vector<uint8_t>& out, size_t n) {
   out.push_back((uint8_t)(n >> 24)); out.push_back((uint8_t)(n >> 16));
   out.push_back((uint8_t)(n >> 8)); out.push_back((uint8_t)n);
-  if (!n) return;
-  const int words = v.group == BH_G1 ? 24 : 48;
-  std::vector<uint32_t> w(n * words);
-  (void)hipMemcpy(w.data(), v.pts.p, n * words * 4, hipMemcpyDeviceToHost);
-  std::vector<char> inf(n, 0);
-  for (size_t k : v.identity_idx) inf[k] = 1;
-  const size_t pb = v.group == BH_G1 ? 96 : 192;
-  const size_t base = out.size();
-  out.resize(base + n * pb);
-  for (size_t i = 0; i < n; i++) {
-    const uint32_t* d = &w[i * words];
-    uint8_t* o = &out[base + i * pb];
-    if (v.group == BH_G1) {
-      g1_to_uncompressed(AffinePt<Fp>{fp_from_dev_words_g1(d), fp_from_dev_words_g1(d + 12), inf[i] != 0}, o);
-    } else {
-      g2_to_uncompressed(AffinePt<bh::Fp2>{bh::Fp2{fp_from_dev_words(d), fp_from_dev_words(d + 12)},
-                                           bh::Fp2{fp_from_dev_words(d + 24), fp_from_dev_words(d + 36)}, inf[i] != 0},
-                         o);
-    }
-  }
+}
+template <class T>
+void put_point(std::vector<uint8_t>& out, const AffinePt<T>& p) {
+  out.resize(out.size() + HostOfField<T>::WIRE);
+  to_uncompressed(p, &out[out.size() - HostOfField<T>::WIRE]);
+}
+
+void write_vec(const bh_srs& v, std::vector<uint8_t>& out) {
+  put_u32be(out, v.n);
+  with_group(v.group, [&](auto g) {
+    using G = decltype(g);
+    std::vector<typename G::Affine> pts;
+    (void)download_points<G>(v, v.n, &pts);
+    for (const auto& p : pts) put_point(out, p);
+  });
+}
+
+// VerifyingKey::write (groth16/mod.rs:139-159): the six points, then ic behind its u32-BE length
+void write_vk(const bh_params* p, std::vector<uint8_t>& v) {
+  put_point(v, p->alpha_g1);
+  put_point(v, p->beta_g1);
+  put_point(v, p->beta_g2);
+  put_point(v, p->gamma_g2);
+  put_point(v, p->delta_g1);
+  put_point(v, p->delta_g2);
+  put_u32be(v, p->ic.size());
+  for (const auto& ic : p->ic) put_point(v, ic);
 }
 
 inline size_t popcount_words(const std::vector<uint64_t>& w, size_t nbits) {
@@ -243,17 +244,17 @@ bh_status bh_params_load(bh_ctx* ctx, const uint8_t* bytes, size_t len, int chec
   p->ctx = ctx;
   Reader r{bytes, bytes + len};
   bh_status s;
-  if ((s = read_g1_vk(r, &p->alpha_g1, false))) return s;
-  if ((s = read_g1_vk(r, &p->beta_g1, false))) return s;
-  if ((s = read_g2_vk(r, &p->beta_g2))) return s;
-  if ((s = read_g2_vk(r, &p->gamma_g2))) return s;
-  if ((s = read_g1_vk(r, &p->delta_g1, false))) return s;
-  if ((s = read_g2_vk(r, &p->delta_g2))) return s;
+  if ((s = read_vk_point(r, &p->alpha_g1, false))) return s;
+  if ((s = read_vk_point(r, &p->beta_g1, false))) return s;
+  if ((s = read_vk_point(r, &p->beta_g2, false))) return s;
+  if ((s = read_vk_point(r, &p->gamma_g2, false))) return s;
+  if ((s = read_vk_point(r, &p->delta_g1, false))) return s;
+  if ((s = read_vk_point(r, &p->delta_g2, false))) return s;
   uint32_t ic_len;
   if (!r.u32be(&ic_len)) return BH_ERR_INVALID_ENCODING;
   p->ic.resize(ic_len);
   for (uint32_t i = 0; i < ic_len; i++)
-    if ((s = read_g1_vk(r, &p->ic[i], true))) return s;
+    if ((s = read_vk_point(r, &p->ic[i], true))) return s;
   if ((s = read_vec(ctx, r, BH_G1, checked, &p->h))) return s;
   if ((s = read_vec(ctx, r, BH_G1, checked, &p->l))) return s;
   if ((s = read_vec(ctx, r, BH_G1, checked, &p->a))) return s;
@@ -278,16 +279,7 @@ bh_status bh_params_sizes(const bh_params* p, size_t out[6]) {
 bh_status bh_params_write(const bh_params* p, uint8_t* out, size_t cap, size_t* written) {
   if (!p || !written) return BH_ERR_INVALID_ARGUMENT;
   std::vector<uint8_t> v;
-  uint8_t b[192];
-  g1_to_uncompressed(p->alpha_g1, b); v.insert(v.end(), b, b + 96);
-  g1_to_uncompressed(p->beta_g1, b); v.insert(v.end(), b, b + 96);
-  g2_to_uncompressed(p->beta_g2, b); v.insert(v.end(), b, b + 192);
-  g2_to_uncompressed(p->gamma_g2, b); v.insert(v.end(), b, b + 192);
-  g1_to_uncompressed(p->delta_g1, b); v.insert(v.end(), b, b + 96);
-  g2_to_uncompressed(p->delta_g2, b); v.insert(v.end(), b, b + 192);
-  const size_t n = p->ic.size();
-  v.push_back((uint8_t)(n >> 24)); v.push_back((uint8_t)(n >> 16)); v.push_back((uint8_t)(n >> 8)); v.push_back((uint8_t)n);
-  for (const auto& ic : p->ic) { g1_to_uncompressed(ic, b); v.insert(v.end(), b, b + 96); }
+  write_vk(p, v);
   write_vec(p->h, v);
   write_vec(p->l, v);
   write_vec(p->a, v);
@@ -447,7 +439,8 @@ bh_status ensure_table(bh_ctx* ctx, bh_srs* srs, int c, size_t lo, size_t hi) {
   const size_t n = hi - lo;
   const size_t bytes = n * W * rec * 4;
   const size_t chunk = std::min<size_t>(n, (size_t)1 << 19);
-  const size_t scratch = g2 ? window_table_scratch_bytes<G2Ops>(chunk, W) : window_table_scratch_bytes<G1Ops>(chunk, W);
+  const size_t scratch =
+      with_group(srs->group, [&](auto g) { return window_table_scratch_bytes<typename decltype(g)::Ops>(chunk, W); });
   {
     // a fresh buffer: multiexp jobs still reading the old table keep it alive until their wait
     std::lock_guard<std::mutex> lk(srs->win_mu);
@@ -467,9 +460,11 @@ bh_status ensure_table(bh_ctx* ctx, bh_srs* srs, int c, size_t lo, size_t hi) {
   BH_TRY_HIP(srs->win->alloc(bytes));
   DevBuf tmp;
   BH_TRY_HIP(tmp.alloc(scratch));
-  const uint32_t* pts = srs->pts.as<uint32_t>() + lo * (g2 ? 48 : 24);
-  if (g2) BH_TRY_HIP(window_table<G2Ops>(pts, n, c, W, srs->win->as<uint32_t>(), rec, tmp.p, chunk, ctx->stream));
-  else BH_TRY_HIP(window_table<G1Ops>(pts, n, c, W, srs->win->as<uint32_t>(), rec, tmp.p, chunk, ctx->stream));
+  BH_TRY_HIP(with_group(srs->group, [&](auto g) {
+    using G = decltype(g);
+    return window_table<typename G::Ops>(srs->pts.as<uint32_t>() + lo * G::WORDS, n, c, W, srs->win->as<uint32_t>(), rec,
+                                         tmp.p, chunk, ctx->stream);
+  }));
   BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
   std::lock_guard<std::mutex> lk(srs->win_mu);
   srs->win_c = c;
@@ -541,13 +536,14 @@ bh_status ensure_h_share(bh_ctx* ctx, bh_params* params, const ShareGeom& g, bh_
   sh->ctx = ctx;
   sh->group = BH_G1;
   sh->n = g.used();
-  BH_TRY_HIP(sh->pts.alloc(std::max<size_t>(sh->n, 1) * 96));
+  BH_TRY_HIP(sh->pts.alloc(std::max<size_t>(sh->n, 1) * G1Host::WORDS * 4));
   const uint8_t* src = params->h.pts.as<uint8_t>();
   uint8_t* dst = sh->pts.as<uint8_t>();
   for (int t = 0; t < g.N; t++) {
     const size_t k0 = (size_t)t * g.M + (size_t)g.rank * g.C;
     const size_t cnt = std::min(g.C, params->h.n > k0 ? params->h.n - k0 : 0);
-    if (cnt) BH_TRY_HIP(hipMemcpyAsync(dst + (size_t)t * g.C * 96, src + k0 * 96, cnt * 96, hipMemcpyDeviceToDevice,
+    constexpr size_t PB = G1Host::WORDS * 4;  // bytes of a packed h base
+    if (cnt) BH_TRY_HIP(hipMemcpyAsync(dst + (size_t)t * g.C * PB, src + k0 * PB, cnt * PB, hipMemcpyDeviceToDevice,
                                        ctx->stream));
   }
   BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
@@ -562,24 +558,6 @@ bh_status ensure_h_share(bh_ctx* ctx, bh_params* params, const ShareGeom& g, bh_
 // sort and bucket reduction on the side streams, beside the accumulations; a host thread
 // computes them (double-and-add, bellman's own per-term cost) while the device works.
 constexpr size_t HOST_INPUT_MSM_MAX = 64;
-
-// the first n points of a device vector, on the host (device Montgomery -> host Montgomery)
-template <bool G2>
-bh_status read_head(const bh_srs& v, size_t n, std::vector<typename std::conditional<G2, AffinePt<bh::Fp2>, AffinePt<Fp>>::type>* out) {
-  const size_t words = G2 ? 48 : 24;
-  std::vector<uint32_t> w(std::max<size_t>(n, 1) * words);
-  if (n) BH_TRY_HIP(hipMemcpy(w.data(), v.pts.p, n * words * 4, hipMemcpyDeviceToHost));
-  out->resize(n);
-  for (size_t i = 0; i < n; i++) {
-    const uint32_t* d = &w[i * words];
-    if constexpr (G2)
-      (*out)[i] = AffinePt<bh::Fp2>{bh::Fp2{fp_from_dev_words(d), fp_from_dev_words(d + 12)},
-                                    bh::Fp2{fp_from_dev_words(d + 24), fp_from_dev_words(d + 36)}, false};
-    else
-      (*out)[i] = AffinePt<Fp>{fp_from_dev_words_g1(d), fp_from_dev_words_g1(d + 12), false};
-  }
-  return BH_OK;
-}
 
 // shard [lo, hi) of the input multiexps -> r_a (a_inputs), r_b1 (b_g1_inputs), r_b2 (b_g2_inputs)
 bh_status host_input_msms(int device, bh_params* p, const bh_witness* w, size_t lo, size_t hi, Jac<Fp>* r_a,
@@ -605,9 +583,9 @@ bh_status host_input_msms(int device, bh_params* p, const bh_witness* w, size_t 
       const size_t na = std::max(hi, p->h_a_head.size());
       const size_t nb2 = std::max(nb_hi, std::max(p->h_b1_head.size(), p->h_b2_head.size()));
       bh_status s;
-      if ((s = read_head<false>(p->a, na, &p->h_a_head))) return s;
-      if ((s = read_head<false>(p->b_g1, nb2, &p->h_b1_head))) return s;
-      if ((s = read_head<true>(p->b_g2, nb2, &p->h_b2_head))) return s;
+      if ((s = download_points<G1Host>(p->a, na, &p->h_a_head))) return s;
+      if ((s = download_points<G1Host>(p->b_g1, nb2, &p->h_b1_head))) return s;
+      if ((s = download_points<G2Host>(p->b_g2, nb2, &p->h_b2_head))) return s;
     }
     a_pts.assign(p->h_a_head.begin() + lo, p->h_a_head.begin() + hi);
     b1_pts.assign(p->h_b1_head.begin() + nb, p->h_b1_head.begin() + nb_hi);
@@ -1176,8 +1154,8 @@ bh_status collect_results(ProofRun& R, const ProofSchedule& P, Jac<Fp> res1[6], 
     float t = 0;
     if (acc_events_on())
       (void)hipEventElapsedTime(&t, ctx->jev[JEV_ACC_BEGIN + 2 * j], ctx->jev[JEV_ACC_END + 2 * j]);
-    if (J.g2) res2[J.out] = combine_g2(ctx->host_out2 + 128 * J.out, R.shapes[j]);
-    else res1[J.out] = combine_g1(ctx->host_out1 + 128 * J.out, R.shapes[j]);
+    if (J.g2) res2[J.out] = combine<G2Host>(ctx->host_out2 + 128 * J.out, R.shapes[j]);
+    else res1[J.out] = combine<G1Host>(ctx->host_out1 + 128 * J.out, R.shapes[j]);
     acc->ms[J.g2] += t;
     acc->launches[J.g2]++;
     acc->pairs[J.g2] += (size_t)((unsigned __int128)J.used * R.len(j) / std::max<size_t>(J.n, 1));
@@ -1419,9 +1397,9 @@ void assemble_finish(const AssemblePre& p, const Jac<Fp> r1[6], const Jac<bh::Fp
   g_c = jac_add(g_c, b1_answer);
   g_c = jac_add(g_c, r1[0]);
   g_c = jac_add(g_c, r1[1]);
-  g1_to_compressed(jac_to_affine(g_a), proof_out);
-  g2_to_compressed(jac_to_affine(g_b), proof_out + 48);
-  g1_to_compressed(jac_to_affine(g_c), proof_out + 144);
+  to_compressed(jac_to_affine(g_a), proof_out);
+  to_compressed(jac_to_affine(g_b), proof_out + 48);
+  to_compressed(jac_to_affine(g_c), proof_out + 144);
 }
 
 void assemble(const VkHost& vk, const Jac<Fp> r1[6], const Jac<bh::Fp2> r2[2], const uint64_t r_in[4],
@@ -1458,11 +1436,11 @@ VkHost vk_of(const bh_params* p) {
   return VkHost{p->alpha_g1, p->beta_g1, p->delta_g1, p->beta_g2, p->delta_g2};
 }
 
-constexpr size_t PARTIAL_BYTES = 6 * 96 + 2 * 192;
+constexpr size_t PARTIAL_BYTES = 6 * G1Host::WIRE + 2 * G2Host::WIRE;
 
 void write_partial(const Jac<Fp> r1[6], const Jac<bh::Fp2> r2[2], uint8_t* out) {
-  for (int i = 0; i < 6; i++) g1_to_uncompressed(jac_to_affine(r1[i]), out + 96 * i);
-  for (int i = 0; i < 2; i++) g2_to_uncompressed(jac_to_affine(r2[i]), out + 576 + 192 * i);
+  for (int i = 0; i < 6; i++) to_uncompressed(jac_to_affine(r1[i]), out + G1Host::WIRE * i);
+  for (int i = 0; i < 2; i++) to_uncompressed(jac_to_affine(r2[i]), out + 6 * G1Host::WIRE + G2Host::WIRE * i);
 }
 
 // N virtual ranks of one device, one host thread each: the all-to-all as device copies.
@@ -1882,20 +1860,12 @@ bh_status bh_prove_witness_partials_ranks(bh_ctx* const* ctxs, const bh_params* 
 
 bh_status bh_vk_write(const bh_params* p, uint8_t* out, size_t cap, size_t* written) {
   if (!p || !written) return BH_ERR_INVALID_ARGUMENT;
-  const size_t need = 96 * 3 + 192 * 3 + 4 + 96 * p->ic.size();
-  *written = need;
+  std::vector<uint8_t> v;
+  write_vk(p, v);
+  *written = v.size();
   if (!out) return BH_OK;
-  if (cap < need) return BH_ERR_INVALID_ARGUMENT;
-  uint8_t* o = out;
-  g1_to_uncompressed(p->alpha_g1, o); o += 96;
-  g1_to_uncompressed(p->beta_g1, o); o += 96;
-  g2_to_uncompressed(p->beta_g2, o); o += 192;
-  g2_to_uncompressed(p->gamma_g2, o); o += 192;
-  g1_to_uncompressed(p->delta_g1, o); o += 96;
-  g2_to_uncompressed(p->delta_g2, o); o += 192;
-  const size_t n = p->ic.size();
-  o[0] = (uint8_t)(n >> 24); o[1] = (uint8_t)(n >> 16); o[2] = (uint8_t)(n >> 8); o[3] = (uint8_t)n; o += 4;
-  for (const auto& ic : p->ic) { g1_to_uncompressed(ic, o); o += 96; }
+  if (cap < v.size()) return BH_ERR_INVALID_ARGUMENT;
+  memcpy(out, v.data(), v.size());
   return BH_OK;
 }
 
@@ -1904,18 +1874,20 @@ bh_status bh_vk_write(const bh_params* p, uint8_t* out, size_t cap, size_t* writ
 bh_status bh_proof_from_partials(const uint8_t* vk_bytes, size_t vk_len, const uint8_t* partials, size_t nshards,
                                  const uint64_t r[4], const uint64_t s[4], uint8_t proof_out[192]) {
   if (!vk_bytes || !partials || !nshards || !r || !s || !proof_out) return BH_ERR_INVALID_ARGUMENT;
-  if (vk_len < 96 * 3 + 192 * 3) return BH_ERR_INVALID_ENCODING;
+  if (vk_len < 3 * G1Host::WIRE + 3 * G2Host::WIRE) return BH_ERR_INVALID_ENCODING;
   // on-curve checks only: the VK comes from bh_vk_write of loaded (checked) Parameters and
   // the partials are sums of subgroup points; this runs once per multi-GPU proof
   VkHost vk;
   AffinePt<bh::Fp2> gamma;
   const uint8_t* p = vk_bytes;
-  if (g1_from_uncompressed(p, &vk.alpha_g1, true)) return BH_ERR_INVALID_ENCODING;
-  if (g1_from_uncompressed(p + 96, &vk.beta_g1, true)) return BH_ERR_INVALID_ENCODING;
-  if (g2_from_uncompressed(p + 192, &vk.beta_g2, true)) return BH_ERR_INVALID_ENCODING;
-  if (g2_from_uncompressed(p + 384, &gamma, true)) return BH_ERR_INVALID_ENCODING;
-  if (g1_from_uncompressed(p + 576, &vk.delta_g1, true)) return BH_ERR_INVALID_ENCODING;
-  if (g2_from_uncompressed(p + 672, &vk.delta_g2, true)) return BH_ERR_INVALID_ENCODING;
+  const auto next = [&p](auto* pt) {  // on-curve only
+    const int bad = from_uncompressed(p, pt, true);
+    p += HostOfField<std::decay_t<decltype(pt->x)>>::WIRE;
+    return bad;
+  };
+  if (next(&vk.alpha_g1) || next(&vk.beta_g1) || next(&vk.beta_g2) || next(&gamma) || next(&vk.delta_g1) ||
+      next(&vk.delta_g2))
+    return BH_ERR_INVALID_ENCODING;
   if (vk.delta_g1.infinity || vk.delta_g2.infinity) return BH_ERR_UNEXPECTED_IDENTITY;  // prover.rs:309-313
   Jac<Fp> r1[6];
   Jac<bh::Fp2> r2[2];
@@ -1925,12 +1897,12 @@ bh_status bh_proof_from_partials(const uint8_t* vk_bytes, size_t vk_len, const u
     const uint8_t* q = partials + k * PARTIAL_BYTES;
     for (int i = 0; i < 6; i++) {
       AffinePt<Fp> a;
-      if (g1_from_uncompressed(q + 96 * i, &a, true)) return BH_ERR_INVALID_ENCODING;
+      if (from_uncompressed(q + G1Host::WIRE * i, &a, true)) return BH_ERR_INVALID_ENCODING;
       r1[i] = jac_add(r1[i], jac_from_affine(a));
     }
     for (int i = 0; i < 2; i++) {
       AffinePt<bh::Fp2> a;
-      if (g2_from_uncompressed(q + 576 + 192 * i, &a, true)) return BH_ERR_INVALID_ENCODING;
+      if (from_uncompressed(q + 6 * G1Host::WIRE + G2Host::WIRE * i, &a, true)) return BH_ERR_INVALID_ENCODING;
       r2[i] = jac_add(r2[i], jac_from_affine(a));
     }
   }

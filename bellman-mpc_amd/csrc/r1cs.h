@@ -41,7 +41,7 @@ std::vector<AffinePt<Fp2>> crs_table_g2();
 // crs.hip's fixed_base_batch, in chunks; tab: crs_table_g1 / _g2 on the device.  Synchronises
 // ctx->stream (caller holds ctx->mu)
 template <class C>
-bh_status fixed_base_device(bh_ctx* ctx, const bh_srs& tab, const uint32_t* d_sc, size_t n, int group, bh_srs* out);
+bh_status fixed_base_device(bh_ctx* ctx, const bh_srs& tab, const uint32_t* d_sc, size_t n, bh_srs* out);
 
 // api.hip: the ifft (domain.rs:104-121) of 2^L packed device-Montgomery Fr resident in d_a, natural
 // order in and out, d_tmp the same size; enqueued on ctx->stream (caller holds ctx->mu)

@@ -134,12 +134,12 @@ void r1cs_kernels(std::vector<KernInfo>& v) {
 // n canonical scalars on the device (all non-zero) -> packed affine points, in chunks as
 // chain.hip's fixed_base_to_srs; everything stream-ordered, the scratch shared by the chunks
 template <class C>
-bh_status fixed_base_device(bh_ctx* ctx, const bh_srs& tab, const uint32_t* d_sc, size_t n, int group, bh_srs* out) {
+bh_status fixed_base_device(bh_ctx* ctx, const bh_srs& tab, const uint32_t* d_sc, size_t n, bh_srs* out) {
   out->ctx = ctx;
-  out->group = group;
+  out->group = HostOf<C>::ID;
   out->n = n;
   out->identity_idx.clear();
-  const int words = group == BH_G1 ? 24 : 48;
+  constexpr int words = HostOf<C>::WORDS;
   BH_TRY_HIP(out->pts.alloc(std::max<size_t>(n, 1) * words * 4));
   if (!n) return BH_OK;
   const size_t chunk = std::min<size_t>(n, (size_t)1 << 21);
@@ -155,8 +155,8 @@ bh_status fixed_base_device(bh_ctx* ctx, const bh_srs& tab, const uint32_t* d_sc
   return BH_OK;
 }
 
-template bh_status fixed_base_device<G1Ops>(bh_ctx*, const bh_srs&, const uint32_t*, size_t, int, bh_srs*);
-template bh_status fixed_base_device<G2Ops>(bh_ctx*, const bh_srs&, const uint32_t*, size_t, int, bh_srs*);
+template bh_status fixed_base_device<G1Ops>(bh_ctx*, const bh_srs&, const uint32_t*, size_t, bh_srs*);
+template bh_status fixed_base_device<G2Ops>(bh_ctx*, const bh_srs&, const uint32_t*, size_t, bh_srs*);
 
 }  // namespace bh
 
@@ -454,13 +454,13 @@ bh_status bh_generate_parameters(bh_ctx* ctx, const bh_r1cs* r, const uint64_t a
     d_pow.release();
     // fixed-base multiplications (generator.rs:374-397, 520-572)
     bh_srs tab1, tab2;
-    if ((s = srs_upload_affine(ctx, BH_G1, t1.data(), t1.size(), &tab1))) return s;
-    if ((s = srs_upload_affine(ctx, BH_G2, t2.data(), t2.size(), &tab2))) return s;
-    if ((s = fixed_base_device<G1Ops>(ctx, tab1, d_h.as<uint32_t>(), m - 1, BH_G1, &p->h))) return s;
-    if ((s = fixed_base_device<G1Ops>(ctx, tab1, d_ext.as<uint32_t>() + ni * 8, na, BH_G1, &p->l))) return s;
-    if ((s = fixed_base_device<G1Ops>(ctx, tab1, d_a.as<uint32_t>(), a_n, BH_G1, &p->a))) return s;
-    if ((s = fixed_base_device<G1Ops>(ctx, tab1, d_b.as<uint32_t>(), b_n, BH_G1, &p->b_g1))) return s;
-    if ((s = fixed_base_device<G2Ops>(ctx, tab2, d_b.as<uint32_t>(), b_n, BH_G2, &p->b_g2))) return s;
+    if ((s = srs_upload_affine(ctx, t1.data(), t1.size(), &tab1))) return s;
+    if ((s = srs_upload_affine(ctx, t2.data(), t2.size(), &tab2))) return s;
+    if ((s = fixed_base_device<G1Ops>(ctx, tab1, d_h.as<uint32_t>(), m - 1, &p->h))) return s;
+    if ((s = fixed_base_device<G1Ops>(ctx, tab1, d_ext.as<uint32_t>() + ni * 8, na, &p->l))) return s;
+    if ((s = fixed_base_device<G1Ops>(ctx, tab1, d_a.as<uint32_t>(), a_n, &p->a))) return s;
+    if ((s = fixed_base_device<G1Ops>(ctx, tab1, d_b.as<uint32_t>(), b_n, &p->b_g1))) return s;
+    if ((s = fixed_base_device<G2Ops>(ctx, tab2, d_b.as<uint32_t>(), b_n, &p->b_g2))) return s;
   }
   // ic and the verifying key on the host (ni points); a zero ic scalar is the identity
   auto g1mul = [&](const uint64_t* c) { return jac_to_affine(jac_mul(g1, c, 4)); };

@@ -39,7 +39,7 @@ struct VbField<G2Ops> { using F = Fp2Ops; };
 
 template <class C>
 __device__ __forceinline__ typename C::A vb_load_affine(const uint32_t* base, size_t i) {
-  using F = typename VbField<C>::F;
+  using F = typename FieldOf<C>::F;
   constexpr int PW = F::PACKED_WORDS;
   typename C::A a;
   a.x = F::unpack(base + i * 2 * PW);
@@ -183,7 +183,7 @@ struct VbScratch {
   bh_status alloc(bh_ctx* ctx, size_t n) {
     const size_t chunk = std::min(n, VB_CHUNK);
     BH_TRY_HIP(xyzz.alloc(chunk * sizeof(typename C::P)));
-    BH_TRY_HIP(scr.alloc(chunk * sizeof(typename VbField<C>::F::T) + 64));
+    BH_TRY_HIP(scr.alloc(chunk * sizeof(typename FieldOf<C>::F::T) + 64));
     BH_TRY_HIP(flag.alloc(4));
     BH_TRY_HIP(hipMemsetAsync(flag.p, 0, 4, ctx->stream));
     return BH_OK;
@@ -197,9 +197,9 @@ constexpr size_t VB_WIN_CHUNK = (size_t)1 << 18;
 template <class C>
 bh_status mul_win_t(bh_ctx* ctx, const bh_srs* in, const uint32_t* d_sc, int stride, int nbits, bh_srs* out) {
   using P = typename C::P;
-  using T = typename VbField<C>::F::T;
+  using T = typename FieldOf<C>::F::T;
   const size_t n = in->n;
-  const int words = in->group == BH_G1 ? 24 : 48;
+  constexpr int words = HostOf<C>::WORDS;
   srs_init(ctx, in->group, n, out);
   BH_TRY_HIP(out->pts.alloc(std::max<size_t>(n, 1) * words * 4));
   if (!n) return BH_OK;
@@ -230,7 +230,7 @@ bh_status mul_win_t(bh_ctx* ctx, const bh_srs* in, const uint32_t* d_sc, int str
 
 template <class C>
 bh_status sub_t(bh_ctx* ctx, const bh_srs* in, size_t lo1, size_t lo2, size_t n, bh_srs* out) {
-  const int words = in->group == BH_G1 ? 24 : 48;
+  constexpr int words = HostOf<C>::WORDS;
   srs_init(ctx, in->group, n, out);
   BH_TRY_HIP(out->pts.alloc(std::max<size_t>(n, 1) * words * 4));
   if (!n) return BH_OK;
@@ -253,15 +253,15 @@ bh_status sub_t(bh_ctx* ctx, const bh_srs* in, size_t lo1, size_t lo2, size_t n,
 bh_status varbase_mul(bh_ctx* ctx, const bh_srs* in, const uint32_t* d_sc, int stride, int nbits, bh_srs* out) {
   if (!in->identity_idx.empty()) return BH_ERR_UNEXPECTED_IDENTITY;
   if (nbits < 1 || nbits > 255 || (stride != 0 && stride != 8)) return BH_ERR_INVALID_ARGUMENT;
-  return in->group == BH_G1 ? mul_win_t<G1Ops>(ctx, in, d_sc, stride, nbits, out)
-                            : mul_win_t<G2Ops>(ctx, in, d_sc, stride, nbits, out);
+  return with_group(in->group,
+                    [&](auto g) { return mul_win_t<typename decltype(g)::Ops>(ctx, in, d_sc, stride, nbits, out); });
 }
 
 bh_status varbase_sub(bh_ctx* ctx, const bh_srs* in, size_t lo1, size_t lo2, size_t n, bh_srs* out) {
   if (n > in->n || lo1 > in->n - n || lo2 > in->n - n) return BH_ERR_INVALID_ARGUMENT;
   for (size_t i : in->identity_idx)
     if ((i >= lo1 && i < lo1 + n) || (i >= lo2 && i < lo2 + n)) return BH_ERR_UNEXPECTED_IDENTITY;
-  return in->group == BH_G1 ? sub_t<G1Ops>(ctx, in, lo1, lo2, n, out) : sub_t<G2Ops>(ctx, in, lo1, lo2, n, out);
+  return with_group(in->group, [&](auto g) { return sub_t<typename decltype(g)::Ops>(ctx, in, lo1, lo2, n, out); });
 }
 
 bh_status varbase_power_scalars(bh_ctx* ctx, size_t n, const uint64_t a_w[4], const uint64_t x_w[4], int invert,

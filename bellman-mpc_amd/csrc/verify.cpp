@@ -180,14 +180,14 @@ Fp2 fp2_pow(const Fp2& a, const uint64_t* e, int words) {
   return r;
 }
 
-bool fp_sqrt(const Fp& a, Fp* out) {  // p = 3 mod 4
+bool field_sqrt(const Fp& a, Fp* out) {  // p = 3 mod 4
   const Fp y = pow_vartime(a, pexps().p1_4, 6);
   if (!(sqr(y) == a)) return false;
   *out = y;
   return true;
 }
 
-bool fp2_sqrt(const Fp2& a, Fp2* out) {  // p = 3 mod 4 algorithm over Fp2 = Fp[u]/(u^2 + 1)
+bool field_sqrt(const Fp2& a, Fp2* out) {  // p = 3 mod 4 algorithm over Fp2 = Fp[u]/(u^2 + 1)
   if (a == Fp2::zero()) { *out = a; return true; }
   const Fp2 a1 = fp2_pow(a, pexps().p3_4, 6);
   const Fp2 alpha = mul(sqr(a1), a);
@@ -203,32 +203,18 @@ bool fp2_sqrt(const Fp2& a, Fp2* out) {  // p = 3 mod 4 algorithm over Fp2 = Fp[
   return true;
 }
 
-// G1Affine::from_compressed + Proof::read's identity rejection
-bh_status g1_from_compressed(const uint8_t* in, AffinePt<Fp>* out) {
+// G1Affine / G2Affine::from_compressed + Proof::read's identity rejection
+template <class T>
+bh_status from_compressed(const uint8_t* in, AffinePt<T>* out) {
   const uint8_t flags = in[0] >> 5;
   if (!(flags & 0x4)) return BH_ERR_INVALID_ENCODING;  // compression flag
   if (flags & 0x2) return BH_ERR_INVALID_ENCODING;     // the identity ("point at infinity")
-  Fp x;
-  if (!fp_from_be(in, &x, 0xE0)) return BH_ERR_INVALID_ENCODING;
-  Fp y;
-  if (!fp_sqrt(add(mul(sqr(x), x), CurveB<Fp>::b()), &y)) return BH_ERR_INVALID_ENCODING;
-  if (fp_lex_largest(y) != ((flags & 0x1) != 0)) y = neg(y);
-  out->x = x; out->y = y; out->infinity = false;
-  if (!in_subgroup(*out)) return BH_ERR_NOT_IN_SUBGROUP;
-  return BH_OK;
-}
-
-bh_status g2_from_compressed(const uint8_t* in, AffinePt<Fp2>* out) {
-  const uint8_t flags = in[0] >> 5;
-  if (!(flags & 0x4)) return BH_ERR_INVALID_ENCODING;
-  if (flags & 0x2) return BH_ERR_INVALID_ENCODING;
-  Fp2 x;
-  if (!fp_from_be(in, &x.c1, 0xE0) || !fp_from_be(in + 48, &x.c0)) return BH_ERR_INVALID_ENCODING;
-  Fp2 y;
-  if (!fp2_sqrt(add(mul(sqr(x), x), CurveB<Fp2>::b()), &y)) return BH_ERR_INVALID_ENCODING;
-  const bool lex = fp_lex_largest(y.c1) || (y.c1.is_zero() && fp_lex_largest(y.c0));
-  if (lex != ((flags & 0x1) != 0)) y = neg(y);
-  out->x = x; out->y = y; out->infinity = false;
+  for (int k = 0; k < COMPONENTS<T> / 2; k++)
+    if (!fp_from_be(in + 48 * k, &components(*out)[wire_component<T>(k)], k == 0 ? 0xE0 : 0))
+      return BH_ERR_INVALID_ENCODING;
+  if (!field_sqrt(add(mul(sqr(out->x), out->x), CurveB<T>::b()), &out->y)) return BH_ERR_INVALID_ENCODING;
+  if (lex_largest(out->y) != ((flags & 0x1) != 0)) out->y = neg(out->y);
+  out->infinity = false;
   if (!in_subgroup(*out)) return BH_ERR_NOT_IN_SUBGROUP;
   return BH_OK;
 }
@@ -240,9 +226,9 @@ struct Proof {
 
 bh_status proof_read(const uint8_t* in, Proof* p) {  // Proof::read, groth16/mod.rs:50-103
   bh_status s;
-  if ((s = g1_from_compressed(in, &p->a))) return s;
-  if ((s = g2_from_compressed(in + 48, &p->b))) return s;
-  return g1_from_compressed(in + 144, &p->c);
+  if ((s = from_compressed(in, &p->a))) return s;
+  if ((s = from_compressed(in + 48, &p->b))) return s;
+  return from_compressed(in + 144, &p->c);
 }
 
 struct Vk {
@@ -253,37 +239,31 @@ struct Vk {
 
 bh_status vk_read(const uint8_t* in, size_t len, Vk* vk) {  // VerifyingKey::read, mod.rs:174-222
   size_t o = 0;
-  auto g1 = [&](AffinePt<Fp>* out, bool no_identity) -> bh_status {
-    if (len - o < 96) return BH_ERR_UNEXPECTED_EOF;
-    const int r = g1_from_uncompressed(in + o, out, true, true);
-    o += 96;
+  auto pt = [&](auto* out, bool no_identity) -> bh_status {
+    constexpr size_t pb = HostOfField<std::decay_t<decltype(out->x)>>::WIRE;
+    if (len - o < pb) return BH_ERR_UNEXPECTED_EOF;
+    const int r = from_uncompressed(in + o, out, true, true);
+    o += pb;
     if (r == -3) return BH_ERR_NOT_IN_SUBGROUP;
     if (r) return BH_ERR_INVALID_ENCODING;
     return (no_identity && out->infinity) ? BH_ERR_INVALID_ENCODING : BH_OK;
   };
-  auto g2 = [&](AffinePt<Fp2>* out) -> bh_status {
-    if (len - o < 192) return BH_ERR_UNEXPECTED_EOF;
-    const int r = g2_from_uncompressed(in + o, out, true, true);
-    o += 192;
-    if (r == -3) return BH_ERR_NOT_IN_SUBGROUP;
-    return r ? BH_ERR_INVALID_ENCODING : BH_OK;
-  };
   bh_status s;
-  if ((s = g1(&vk->alpha_g1, false)) || (s = g1(&vk->beta_g1, false)) || (s = g2(&vk->beta_g2)) ||
-      (s = g2(&vk->gamma_g2)) || (s = g1(&vk->delta_g1, false)) || (s = g2(&vk->delta_g2)))
+  if ((s = pt(&vk->alpha_g1, false)) || (s = pt(&vk->beta_g1, false)) || (s = pt(&vk->beta_g2, false)) ||
+      (s = pt(&vk->gamma_g2, false)) || (s = pt(&vk->delta_g1, false)) || (s = pt(&vk->delta_g2, false)))
     return s;
   if (len - o < 4) return BH_ERR_UNEXPECTED_EOF;
   const uint32_t n = ((uint32_t)in[o] << 24) | ((uint32_t)in[o + 1] << 16) | ((uint32_t)in[o + 2] << 8) | in[o + 3];
   o += 4;
-  if ((size_t)n > (len - o) / 96) return BH_ERR_UNEXPECTED_EOF;
+  if ((size_t)n > (len - o) / G1Host::WIRE) return BH_ERR_UNEXPECTED_EOF;
   vk->ic.resize(n);
   for (uint32_t i = 0; i < n; i++)
-    if ((s = g1(&vk->ic[i], true))) return s;
+    if ((s = pt(&vk->ic[i], true))) return s;
   return BH_OK;
 }
 
-AffinePt<Fp> neg_pt(AffinePt<Fp> p) { if (!p.infinity) p.y = neg(p.y); return p; }
-AffinePt<Fp2> neg_pt(AffinePt<Fp2> q) { if (!q.infinity) q.y = neg(q.y); return q; }
+template <class T>
+AffinePt<T> neg_pt(AffinePt<T> p) { if (!p.infinity) p.y = neg(p.y); return p; }
 
 // canonical public inputs (little-endian u64 x 4 each), reduced mod r like Fr::from_repr's
 // callers would have to: a word >= r is an invalid Fr

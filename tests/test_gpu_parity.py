@@ -61,6 +61,84 @@ def test_srs_rejects_bad_points(ctx, golden):
     big[1:48] = b"\xff" * 47  # x >= p
     with pytest.raises(bh.SynthesisError):
         bh.Bases(ctx, bh.BH_G1, bytes(big), checked=False)
+    # G2: the same off-curve rule over Fp2 ...
+    from oracle import bls12_381 as bls
+    good2 = bytes.fromhex(golden["msm_g2"]["bases"][0])
+    raw2 = _off_curve(bh.BH_G2, good2)
+    with pytest.raises(bh.SynthesisError) as e:
+        bh.Bases(ctx, bh.BH_G2, raw2, checked=True)
+    assert e.value.code == 12
+    bh.Bases(ctx, bh.BH_G2, raw2, checked=False)
+    # ... and a component >= p in any of the four 48-byte slots (x.c1, x.c0, y.c1, y.c0) is an
+    # invalid encoding even unchecked (p's top byte 0x1a leaves slot 0's flag bits clear)
+    for slot in range(4):
+        big2 = bytearray(good2)
+        big2[48 * slot:48 * slot + 48] = bls.P.to_bytes(48, "big")
+        with pytest.raises(bh.SynthesisError) as e:
+            bh.Bases(ctx, bh.BH_G2, bytes(big2), checked=False)
+        assert e.value.code == 11, slot
+
+
+def _group_bases(golden, group):
+    """(wire bytes per point, the golden bases' encodings, the oracle's unchecked decoder and curve)"""
+    from oracle import bls12_381 as bls
+    if group == _bh().BH_G1:
+        return 96, [bytes.fromhex(h) for h in golden["msm_g1"]["bases"]], bls.g1_from_uncompressed, bls.G1
+    return 192, [bytes.fromhex(h) for h in golden["msm_g2"]["bases"]], bls.g2_from_uncompressed, bls.G2
+
+
+def _off_curve(group, enc):
+    """enc with the low bit of its last byte (y, or y.c0) flipped: still a valid encoding, every
+    component < p, no longer on the curve (checked here on the CPU)"""
+    from oracle import bls12_381 as bls
+    dec, curve = (bls.g1_from_uncompressed, bls.G1) if group == _bh().BH_G1 else (bls.g2_from_uncompressed, bls.G2)
+    ok, good = dec(enc, checked=False)
+    assert ok and curve.on_curve_affine(good)
+    raw = bytearray(enc)
+    raw[-1] ^= 1
+    ok, pt = dec(bytes(raw), checked=False)  # ok: flags clear, every component < p
+    assert ok and pt is not None and not curve.on_curve_affine(pt)
+    return bytes(raw)
+
+
+@pytest.mark.parametrize("g2", [False, True])
+def test_srs_checks_at_a_block_edge_and_skip_identities(ctx, golden, g2):
+    """257 points: the conversion and check kernels run 256 threads per block, so index 255 is a
+    block's last thread and 256 the only live thread of the next.  An off-curve point at either is
+    found; identity encodings (0x40, then zeros) at 0 and 256 pass the checked read, are skipped by
+    the curve check and come back as the identity; their neighbours round-trip."""
+    bh = _bh()
+    group = bh.BH_G2 if g2 else bh.BH_G1
+    width, encs, dec, curve = _group_bases(golden, group)
+    pts = [encs[i % len(encs)] for i in range(257)]
+    for i in (1, 255, 256):
+        ok, pt = dec(pts[i], checked=False)
+        assert ok and curve.on_curve_affine(pt)
+    for at in (255, 256):
+        bad = list(pts)
+        bad[at] = _off_curve(group, pts[at])
+        with pytest.raises(bh.SynthesisError) as e:
+            bh.Bases(ctx, group, b"".join(bad), checked=True)
+        assert e.value.code == 12, at
+    identity = bytes([0x40]) + bytes(width - 1)
+    withid = list(pts)
+    withid[0] = withid[256] = identity
+    b = bh.Bases(ctx, group, b"".join(withid), checked=True)
+    assert len(b) == 257
+    for i in (0, 256):
+        assert b.get(i) == identity
+    for i in (1, 255):
+        assert b.get(i) == pts[i]
+
+
+@pytest.mark.parametrize("g2", [False, True])
+def test_srs_of_one_identity(ctx, g2):
+    bh = _bh()
+    group = bh.BH_G2 if g2 else bh.BH_G1
+    identity = bytes([0x40]) + bytes((192 if g2 else 96) - 1)
+    for checked in (True, False):
+        b = bh.Bases(ctx, group, identity, checked=checked)
+        assert len(b) == 1 and b.get(0) == identity
 
 
 def test_msm_g1_golden(ctx, golden):
