@@ -66,8 +66,13 @@ class UnconstrainedVariable(SynthesisError):
     pass
 
 
+class PairingDegenerate(SynthesisError):
+    """BH_ERR_PAIRING_DEGENERATE: the device Miller loop met a zero denominator."""
+
+
+BH_ERR_PAIRING_DEGENERATE = 16
 _ERRS = {1: UnexpectedIdentity, 2: UnexpectedEof, 3: PolynomialDegreeTooLarge, 4: DensitySizeMismatch,
-         5: UnconstrainedVariable}
+         5: UnconstrainedVariable, BH_ERR_PAIRING_DEGENERATE: PairingDegenerate}
 
 
 def _load():
@@ -180,6 +185,9 @@ def _load():
         "bh_mpc_uncommon_contribute": (I, [P, P, P, P, P]),
         "bh_mpc_uncommon_verify": (I, [P, P, P, P, P, S, P, P]),
         "bh_mpc_last_miller_ms": (ctypes.c_double, []),
+        "bh_mpc_last_miller_device": (I, []),
+        "bh_miller_product": (I, [P, P, S, P, S, S, P]),
+        "bh_final_exponentiation": (I, [P, P]),
     }
     for kind in ("common", "uncommon"):
         for who in ("", "_contrib"):
@@ -220,7 +228,7 @@ EXPORTED_SYMBOLS = [
     "bh_chain_r1cs", "bh_srs_mul_each", "bh_srs_mul_each_bounded", "bh_srs_mul_powers", "bh_srs_sub_range",
     "bh_mpc_common_initial", "bh_mpc_common_contribute", "bh_mpc_common_verify", "bh_mpc_common_h_basis",
     "bh_mpc_common_len", "bh_mpc_uncommon_initial", "bh_mpc_uncommon_contribute", "bh_mpc_uncommon_verify",
-    "bh_mpc_last_miller_ms",
+    "bh_mpc_last_miller_ms", "bh_mpc_last_miller_device", "bh_miller_product", "bh_final_exponentiation",
 ] + [f"bh_mpc_{kind}{who}_{op}" for kind in ("common", "uncommon") for who in ("", "_contrib")
      for op in ("free", "vector", "point", "write", "read")]
 BH_VEC_H, BH_VEC_L, BH_VEC_A, BH_VEC_B_G1, BH_VEC_B_G2 = range(5)
@@ -1312,6 +1320,42 @@ def verify_batch(vk_bytes, proofs, public_inputs, zs):
     _check(_lib.bh_verify_batch(_ptr(vk), vk.size, _ptr(pf), _ptr(ins), ni, k, _ptr(z), ctypes.byref(ok)),
            "verify_batch")
     return bool(ok.value)
+
+
+def _f12_from_bytes(b):
+    c = [int.from_bytes(b[48 * k:48 * k + 48], "big") for k in range(12)]
+    return [(c[2 * i], c[2 * i + 1]) for i in range(6)]
+
+
+def _f12_to_bytes(f):
+    return b"".join(int(x).to_bytes(48, "big") for c in f for x in c)
+
+
+def multi_miller_loop(ctx, g1_bases, g2_bases, off1=0, off2=0, n=None):
+    """prod_i f(g1_bases[off1 + i], g2_bases[off2 + i]), i < n (default: the rest of g1_bases),
+    before the final exponentiation, computed on the device (bh_miller_product): six pairs of
+    ints, the Fp2 coefficients of w^0..w^5 -- the value of oracle/pairing.py's
+    multi_miller_loop.  Raises PairingDegenerate for a twist point that makes a step divide by
+    zero (none of the order-r subgroup does)."""
+    if n is None:
+        n = len(g1_bases) - off1
+    out = np.zeros(576, dtype=np.uint8)
+    _check(_lib.bh_miller_product(ctx.h, g1_bases.h, off1, g2_bases.h, off2, n, _ptr(out)), "bh_miller_product")
+    return _f12_from_bytes(out.tobytes())
+
+
+def final_exponentiation(f):
+    """f^((p^12 - 1) / r) on the host, for a value in multi_miller_loop's form."""
+    src = np.frombuffer(_f12_to_bytes(f), dtype=np.uint8)
+    out = np.zeros(576, dtype=np.uint8)
+    _check(_lib.bh_final_exponentiation(_ptr(src), _ptr(out)), "bh_final_exponentiation")
+    return _f12_from_bytes(out.tobytes())
+
+
+def pairing_product_is_one(ctx, g1_bases, g2_bases):
+    """prod_i e(g1_bases[i], g2_bases[i]) == 1 for two device vectors of one length."""
+    assert len(g1_bases) == len(g2_bases)
+    return final_exponentiation(multi_miller_loop(ctx, g1_bases, g2_bases)) == [(1, 0)] + [(0, 0)] * 5
 
 
 def device_count():

@@ -620,6 +620,7 @@ const char* bh_status_string(bh_status s) {
     case BH_ERR_NOT_IN_SUBGROUP: return "point is not in the prime-order subgroup";
     case BH_ERR_SCRATCH_LIMIT: return "a kernel's scratch would exceed the device's scratch limit";
     case BH_ERR_NOT_ON_CURVE: return "point not on curve";
+    case BH_ERR_PAIRING_DEGENERATE: return "the Miller loop met a zero denominator (a point outside the subgroup)";
     case BH_ERR_OUT_OF_MEMORY: return "device out of memory";
     case BH_ERR_HIP: return "HIP runtime error";
     default: return "unknown status";

@@ -228,6 +228,10 @@ extern "C" bh_status bh_selftest_scalars_prepare(int device, const uint32_t* in,
                                                  uint32_t* out);
 extern "C" bh_status bh_selftest_density_index(int device, const uint64_t* words, size_t n, uint32_t base_offset,
                                                int32_t* idx);
+// pairing_dev.hip (tests/test_gpu_pairing.py): bh_miller_product with K pairs per lane forced
+// (1..16), so that small inputs reach a lane's batch edge, the wave edge and a short last lane
+extern "C" bh_status bh_selftest_miller_product(bh_ctx* ctx, const bh_srs* g1, size_t off1, const bh_srs* g2,
+                                                size_t off2, size_t n, int K, uint8_t out[576]);
 // prover.hip (tests/test_proof_schedule_cpu.py): proof_schedule() of proof_schedule.h on flat arrays
 extern "C" int bh_selftest_proof_schedule(const uint64_t* jobs, const uint8_t* rel, unsigned flags, int64_t* out,
                                           size_t cap);

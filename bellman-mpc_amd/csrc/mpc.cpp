@@ -13,12 +13,14 @@
 // side is varbase.hip's per-element multiplication for the results and crs.hip's fixed-base path
 // for the "mine" lists; the verifier batches the reference's per-element pairing checks with the
 // caller's random z_i over verify.cpp's Miller loop.
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <memory>
 
 #include "pairing.h"
+#include "pairing_dev.h"
 #include "r1cs.h"
 #include "varbase.h"
 
@@ -180,9 +182,14 @@ Fp12 pooled_miller(bh_ctx* ctx, const std::vector<AffinePt<Fp>>& p, const std::v
 
 // One vector pair of verify_common_paramter (mpc.rs:842-854), batched with z:
 //   (1) e(S1, -G2) prod_i e(z_i O1_i, M2_i) == 1,  (2) e(S1, G2) == e(G1, S2),
-// S1 = sum z_i R1_i, S2 = sum z_i R2_i.  miller_ms: host wall time of the len Miller loops.
+// S1 = sum z_i R1_i, S2 = sum z_i R2_i.  The len Miller loops of (1) run on the device
+// (pairing_dev.hip) over the device vectors z_i O1_i and M2; on the host's pool threads instead
+// when BH_MPC_HOST_MILLER=1 is set (a diagnostic mode, like BH_PROVER_SERIAL) and when the device
+// product reports a zero denominator, which only an M2 element outside the subgroup can cause: such
+// a contribution gets the host loop's verdict, whatever that is.  miller_ms: wall time of the len
+// Miller loops on whichever path ran; on_device: counts the pairs whose loops ran on the device.
 bh_status verify_tau_pair(bh_ctx* ctx, const MpcStorage* st, const MpcContrib* c, int j, const uint32_t* d_z,
-                          int nbits, bool* ok, double* miller_ms) {
+                          int nbits, bool* ok, double* miller_ms, int* on_device) {
   AffinePt<Fp> s1;
   AffinePt<Fp2> s2;
   bh_status s = msm(ctx, c->res[2 * j].get(), d_z, &s1);
@@ -190,14 +197,31 @@ bh_status verify_tau_pair(bh_ctx* ctx, const MpcStorage* st, const MpcContrib* c
   if ((s = msm(ctx, c->res[2 * j + 1].get(), d_z, &s2))) return s;
   bh_srs q;
   if ((s = varbase_mul(ctx, st->v[2 * j].get(), d_z, 8, nbits, &q))) return s;
-  std::vector<AffinePt<Fp>> qh;
-  std::vector<AffinePt<Fp2>> m2;
-  if ((s = download(&q, &qh))) return s;
-  if ((s = download(c->mine[2 * j + 1].get(), &m2))) return s;
+  const bh_srs* mine2 = c->mine[2 * j + 1].get();
   const AffinePt<Fp2> g2 = g2_gen(), ng2 = pt_neg(g2);
-  const auto t0 = std::chrono::steady_clock::now();
-  Fp12 f = pooled_miller(ctx, qh, m2);
-  if (miller_ms) *miller_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  const char* env = getenv("BH_MPC_HOST_MILLER");
+  bool host = env && env[0] == '1';
+  Fp12 f;
+  auto t0 = std::chrono::steady_clock::now();
+  auto add_ms = [&] {
+    if (miller_ms) *miller_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  };
+  if (!host) {
+    s = miller_product_device(ctx, &q, 0, mine2, 0, q.n, 0, &f);
+    add_ms();
+    if (s == BH_ERR_PAIRING_DEGENERATE) host = true;
+    else if (s) return s;
+    else if (on_device) ++*on_device;
+  }
+  if (host) {
+    std::vector<AffinePt<Fp>> qh;
+    std::vector<AffinePt<Fp2>> m2;
+    if ((s = download(&q, &qh))) return s;
+    if ((s = download(mine2, &m2))) return s;
+    t0 = std::chrono::steady_clock::now();
+    f = pooled_miller(ctx, qh, m2);
+    add_ms();
+  }
   f = f12_mul(f, multi_miller_loop({{s1, ng2}}));
   *ok = f12_is_one(final_exponentiation(f)) && pairing_product_is_one({{s1, ng2}, {g1_gen(), s2}});
   return BH_OK;
@@ -429,6 +453,7 @@ struct CtxLock {
   if (bh_status _s = scratch_check(ctx)) return _s
 
 thread_local double g_miller_ms = 0;
+thread_local int g_miller_device = 0;
 
 }  // namespace
 
@@ -487,6 +512,7 @@ bh_status bh_mpc_common_verify(bh_ctx* ctx, const bh_mpc_common* st, const bh_mp
   if (len && !z) return BH_ERR_INVALID_ARGUMENT;
   MPC_ENTER(ctx);
   g_miller_ms = 0;
+  g_miller_device = 0;
   DevBuf d_z;
   int nbits = 1;
   bh_status s = upload_z(ctx, z, len, &d_z, &nbits);
@@ -499,7 +525,8 @@ bh_status bh_mpc_common_verify(bh_ctx* ctx, const bh_mpc_common* st, const bh_mp
   // alpha_mul_tau and beta_mul_tau (mpc.rs:842-854); the reference's check of the tau list
   // itself is commented out (mpc.rs:831-840) and result_tau stays true
   for (int j = 1; j < 3 && ok; j++)
-    if ((s = verify_tau_pair(ctx, st, c, j, d_z.as<uint32_t>(), nbits, &ok, &g_miller_ms))) return s;
+    if ((s = verify_tau_pair(ctx, st, c, j, d_z.as<uint32_t>(), nbits, &ok, &g_miller_ms, &g_miller_device)))
+      return s;
   if (!ok) return BH_OK;
   if ((s = to_storage(ctx, c, next))) return s;
   *valid = 1;
@@ -706,7 +733,9 @@ bh_status bh_mpc_uncommon_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t
   return contrib_read(ctx, bytes, len, checked, false, out);
 }
 
-// host wall time (ms) of the per-element Miller loops of this thread's last bh_mpc_common_verify
+// wall time (ms) of the per-element Miller loops of this thread's last bh_mpc_common_verify, and
+// how many of its vector pairs ran them on the device
 double bh_mpc_last_miller_ms(void) { return g_miller_ms; }
+int bh_mpc_last_miller_device(void) { return g_miller_device; }
 
 }  // extern "C"

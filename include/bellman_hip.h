@@ -74,7 +74,8 @@ typedef int bh_status;
 #define BH_ERR_NOT_IN_SUBGROUP 14       /* same reference error: not torsion-free */
 #define BH_ERR_OUT_OF_MEMORY 13
 #define BH_ERR_SCRATCH_LIMIT 15          /* a kernel's spill scratch would exceed the device's limit (no reference counterpart) */
-#define BH_ERR_HIP 100                   /* HIP runtime / device failure */
+#define BH_ERR_PAIRING_DEGENERATE 16     /* the device Miller loop met a zero denominator: a twist point outside the order-r subgroup (no reference counterpart) */
+#define BH_ERR_HIP 100                  /* HIP runtime / device failure */
 
 #define BH_G1 1
 #define BH_G2 2
@@ -545,8 +546,30 @@ bh_status bh_mpc_uncommon_contrib_write(const bh_mpc_uncommon_contrib* contrib, 
                                         size_t* written);
 bh_status bh_mpc_uncommon_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
                                        bh_mpc_uncommon_contrib** out);
-/* host wall time (ms) the per-element Miller loops took in this thread's last bh_mpc_common_verify */
+/* wall time (ms) the per-element Miller loops took in this thread's last bh_mpc_common_verify, on
+ * whichever path ran them: the device product below (the default), or the host's pool threads
+ * (with BH_MPC_HOST_MILLER=1 in the environment, a diagnostic mode, and for a vector pair whose
+ * device product reported BH_ERR_PAIRING_DEGENERATE, so that the verdict is the host's) */
 double bh_mpc_last_miller_ms(void);
+/* how many vector pairs of that verification ran their Miller loops on the device */
+int bh_mpc_last_miller_device(void);
+
+/* ---- pairing products over device vectors.
+ * bh_miller_product: prod_{i < n} f(g1[off1 + i], g2[off2 + i]) before the final exponentiation --
+ * multi_miller_loop of the bls12_381 crate as verifier.rs and mpc.rs:787-804 use it -- computed on
+ * the device for a G1 and a G2 vector of the context's device.  Conventions as the library's host
+ * verifier: Fp12 = Fp2[w]/(w^6 - xi), xi = 1 + u; affine line functions scaled by w^3; the loop over
+ * |x| (the sign of x only inverts every value, so a product-equals-one check is unaffected); a pair
+ * with an identity on either side contributes one.  out: the twelve Fp coefficients c[0].c0,
+ * c[0].c1, ..., c[5].c1 of sum_k c[k] w^k, 48 bytes big-endian canonical each (the byte convention
+ * of point coordinates); n = 0 gives one.  BH_ERR_INVALID_ARGUMENT: a null pointer, g1 not a G1 or
+ * g2 not a G2 vector, a range past a vector's end.  BH_ERR_PAIRING_DEGENERATE: a step met a zero
+ * denominator, which no point of the order-r subgroup causes; out is then not written.
+ * bh_final_exponentiation: out = f^((p^12 - 1) / r) in the same encoding (host only, no context);
+ * BH_ERR_INVALID_ENCODING for a coefficient >= p. */
+bh_status bh_miller_product(bh_ctx* ctx, const bh_srs* g1, size_t off1, const bh_srs* g2, size_t off2, size_t n,
+                            uint8_t out[576]);
+bh_status bh_final_exponentiation(const uint8_t f[576], uint8_t out[576]);
 
 /* Parameters::write of device-resident params (for parity tests; host copy). */
 bh_status bh_params_write(const bh_params* p, uint8_t* out, size_t cap, size_t* written);

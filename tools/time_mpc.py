@@ -7,11 +7,14 @@
   * the same length through k_fixed_base (the "mine" lists of a contribution; read it from the
     kernel statistics of a profiler run of this tool, it has no API of its own);
   * one full round-one contribution at that length;
-  * one verification at 2^log_verify (the host's Miller loops dominate it: len + 1 per vector
-    pair), with the host's Miller-loop share shown separately.
+  * one verification at each 2^log_verify, --reps runs after one warm-up, on both paths of its
+    len Miller loops per vector pair: the device product (the default) and the host's pool threads
+    (BH_MPC_HOST_MILLER=1, which the library reads at every verification), with the Miller share
+    shown separately.  Sizes above --host-max-log time the device path only (the host path is
+    minutes per run there).
 
 Every call synchronises, so host wall time is the device time plus the call's allocations.
-usage: time_mpc.py [--log-len 20] [--log-verify 10] [--reps 3]"""
+usage: time_mpc.py [--log-len 20] [--log-verify 10 [16 20 ...]] [--host-max-log 10] [--reps 3]"""
 import argparse
 import json
 import os
@@ -33,7 +36,8 @@ def timed(fn):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-len", type=int, default=20)
-    ap.add_argument("--log-verify", type=int, default=10)
+    ap.add_argument("--log-verify", type=int, nargs="+", default=[10])
+    ap.add_argument("--host-max-log", type=int, default=10)
     ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
     import bellman_hip as bh
@@ -58,15 +62,33 @@ def main():
     out["contribution_ms"] = round(ms, 1)
     del c, vec, st0
 
-    nv = 1 << args.log_verify
-    st = bh.initial_common_paramters(ctx, nv)
-    c = bh.mpc_common_paramters_generator(ctx, st, (a, x, a ^ x))
-    z = bh.random_z(nv)
-    nxt, ms = timed(lambda: bh.verify_common_paramter(ctx, st, c, z=z))
-    assert nxt is not None
-    miller = bh.lib().bh_mpc_last_miller_ms()
-    out["verify"] = {"len": nv, "total_ms": round(ms, 1), "host_miller_ms": round(miller, 1),
-                     "miller_loops": 2 * nv, "ms_per_miller_loop_per_thread_pool": round(miller / (2 * nv), 4)}
+    out["verify"] = []
+    for log_verify in args.log_verify:
+        nv = 1 << log_verify
+        st = bh.initial_common_paramters(ctx, nv)
+        c = bh.mpc_common_paramters_generator(ctx, st, (a, x, a ^ x))
+        z = bh.random_z(nv)
+        rec = {"len": nv, "miller_loops": 2 * nv}
+        for path in ("device", "host"):
+            if path == "host" and log_verify > args.host_max_log:
+                continue
+            os.environ["BH_MPC_HOST_MILLER"] = "1" if path == "host" else "0"
+            total, miller = [], []
+            for _ in range(args.reps + 1):
+                nxt, ms = timed(lambda: bh.verify_common_paramter(ctx, st, c, z=z))
+                assert nxt is not None
+                assert bh.lib().bh_mpc_last_miller_device() == (2 if path == "device" else 0)
+                total.append(ms)
+                miller.append(bh.lib().bh_mpc_last_miller_ms())
+            total, miller = total[1:], miller[1:]
+            rec[path] = {"total_ms": [round(v, 1) for v in total], "miller_ms": [round(v, 1) for v in miller],
+                         "median_total_ms": round(statistics.median(total), 1),
+                         "median_miller_ms": round(statistics.median(miller), 1),
+                         "spread_total_ms": round(max(total) - min(total), 1),
+                         "pairs_per_s": round(2 * nv / statistics.median(miller) * 1e3)}
+        os.environ.pop("BH_MPC_HOST_MILLER", None)
+        out["verify"].append(rec)
+        del st, c
     print(json.dumps(out))
     ctx.close()
 
