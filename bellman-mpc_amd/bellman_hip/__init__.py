@@ -188,6 +188,8 @@ def _load():
         "bh_mpc_last_miller_device": (I, []),
         "bh_miller_product": (I, [P, P, S, P, S, S, P]),
         "bh_final_exponentiation": (I, [P, P]),
+        "bh_verify_batch_device": (I, [P, P, S, P, P, S, S, P, P]),
+        "bh_proofs_decode": (I, [P, P, S, P, P, P, P]),
     }
     for kind in ("common", "uncommon"):
         for who in ("", "_contrib"):
@@ -229,6 +231,7 @@ EXPORTED_SYMBOLS = [
     "bh_mpc_common_initial", "bh_mpc_common_contribute", "bh_mpc_common_verify", "bh_mpc_common_h_basis",
     "bh_mpc_common_len", "bh_mpc_uncommon_initial", "bh_mpc_uncommon_contribute", "bh_mpc_uncommon_verify",
     "bh_mpc_last_miller_ms", "bh_mpc_last_miller_device", "bh_miller_product", "bh_final_exponentiation",
+    "bh_verify_batch_device", "bh_proofs_decode",
 ] + [f"bh_mpc_{kind}{who}_{op}" for kind in ("common", "uncommon") for who in ("", "_contrib")
      for op in ("free", "vector", "point", "write", "read")]
 BH_VEC_H, BH_VEC_L, BH_VEC_A, BH_VEC_B_G1, BH_VEC_B_G2 = range(5)
@@ -1320,6 +1323,68 @@ def verify_batch(vk_bytes, proofs, public_inputs, zs):
     _check(_lib.bh_verify_batch(_ptr(vk), vk.size, _ptr(pf), _ptr(ins), ni, k, _ptr(z), ctypes.byref(ok)),
            "verify_batch")
     return bool(ok.value)
+
+
+def verify_batch_device(ctx, vk_bytes, proofs, public_inputs, zs):
+    """verify_batch with the per-proof work on ctx's device (bh_verify_batch_device): the same
+    arguments, verdicts and errors."""
+    k = len(proofs)
+    vk = np.frombuffer(bytes(vk_bytes), dtype=np.uint8)
+    pf = np.frombuffer(b"".join(bytes(p) for p in proofs) or b"\0", dtype=np.uint8)
+    ni = len(public_inputs[0]) if k else 0
+    flat = [x for row in public_inputs for x in row]
+    ins = fr_to_canonical_limbs(flat) if flat else np.zeros((1, 4), dtype=np.uint64)
+    z = fr_to_canonical_limbs(zs) if zs else np.zeros((1, 4), dtype=np.uint64)
+    ok = ctypes.c_int()
+    _check(_lib.bh_verify_batch_device(ctx.h, _ptr(vk), vk.size, _ptr(pf), _ptr(ins), ni, k, _ptr(z),
+                                       ctypes.byref(ok)), "verify_batch_device")
+    return bool(ok.value)
+
+
+def proofs_decode(ctx, proofs):
+    """Proof::read of a list of 192-byte proofs on the device (bh_proofs_decode) -> (A, B, C,
+    statuses): three Bases of len(proofs) points (G1, G2, G1) and a list of zeros, or, when a
+    proof is malformed, (None, None, None, statuses) with the BH_ERR_* code of each proof's first
+    failing point."""
+    k = len(proofs)
+    pf = np.frombuffer(b"".join(bytes(p) for p in proofs) or b"\0", dtype=np.uint8)
+    assert k == 0 or pf.size == 192 * k
+    st = np.zeros(max(k, 1), dtype=np.uint32)
+    ha, hb, hc = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    code = _lib.bh_proofs_decode(ctx.h, _ptr(pf), k, _ptr(st), ctypes.byref(ha), ctypes.byref(hb), ctypes.byref(hc))
+    statuses = [int(x) for x in st[:k]]
+    if any(statuses):
+        assert code == next(s for s in statuses if s) and not (ha.value or hb.value or hc.value)
+        return None, None, None, statuses
+    _check(code, "bh_proofs_decode")
+    return (Bases._adopt(ctx, BH_G1, ha), Bases._adopt(ctx, BH_G2, hb), Bases._adopt(ctx, BH_G1, hc), statuses)
+
+
+class Verifier:
+    """The batch verifier's queue (verifier/batch.rs:95-169): queue((proof, public_inputs)) any
+    number of times, then verify(zs_or_rng, vk_bytes, ctx=None) -- with a Context on its device
+    (verify_batch_device), without one on the host (verify_batch).  zs_or_rng: one nonzero scalar
+    below r per queued proof, or an object with randrange (random.Random, random.SystemRandom)
+    that draws them."""
+
+    def __init__(self):
+        self.items = []
+
+    def queue(self, item):
+        proof, inputs = item
+        self.items.append((bytes(proof), list(inputs)))
+
+    def verify(self, zs_or_rng, vk_bytes, ctx=None):
+        if hasattr(zs_or_rng, "randrange"):
+            zs = [zs_or_rng.randrange(1, R_MODULUS) for _ in self.items]
+        else:
+            zs = list(zs_or_rng)
+        assert len(zs) == len(self.items)
+        proofs = [p for p, _ in self.items]
+        inputs = [i for _, i in self.items]
+        if ctx is None:
+            return verify_batch(vk_bytes, proofs, inputs, zs)
+        return verify_batch_device(ctx, vk_bytes, proofs, inputs, zs)
 
 
 def _f12_from_bytes(b):

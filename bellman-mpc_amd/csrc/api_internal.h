@@ -232,6 +232,11 @@ extern "C" bh_status bh_selftest_density_index(int device, const uint64_t* words
 // (1..16), so that small inputs reach a lane's batch edge, the wave edge and a short last lane
 extern "C" bh_status bh_selftest_miller_product(bh_ctx* ctx, const bh_srs* g1, size_t off1, const bh_srs* g2,
                                                 size_t off2, size_t n, int K, uint8_t out[576]);
+// proofs_dev.hip (tests/test_gpu_verify_device.py): the square-root routine the proof decode
+// kernels call, on n caller-chosen canonical values (field 1: Fp, 12 LE words each; 2: Fp2, c0 then
+// c1; a value >= p: BH_ERR_INVALID_ARGUMENT).  out per value: the is-square flag (1 / 0), then the
+// canonical root the routine left (12 or 24 words; a root of the value when the flag is 1)
+extern "C" bh_status bh_selftest_field_sqrt(int device, int field, const uint32_t* in, size_t n, uint32_t* out);
 // prover.hip (tests/test_proof_schedule_cpu.py): proof_schedule() of proof_schedule.h on flat arrays
 extern "C" int bh_selftest_proof_schedule(const uint64_t* jobs, const uint8_t* rel, unsigned flags, int64_t* out,
                                           size_t cap);

@@ -9,13 +9,19 @@
 // The sign of x only inverts every pairing value, so the product-equals-one checks below (the
 // form both reference verifiers use) are unaffected.  Proofs are decoded like Proof::read
 // (groth16/mod.rs:50-103: compressed, torsion-checked, identity rejected), verifying keys like
-// VerifyingKey::read (mod.rs:174-222).  Host-only code: no device is needed.
+// VerifyingKey::read (mod.rs:174-222).  bh_verify_proof and bh_verify_batch are host-only code: no
+// device is needed.  bh_verify_batch_device, at the end, is the batch verifier with its per-proof
+// work on the device and the same statuses and verdicts.
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "api_internal.h"
 #include "pairing.h"
+#include "pairing_dev.h"
+#include "proofs_dev.h"
+#include "varbase.h"
 
 using namespace bh;
 
@@ -343,6 +349,79 @@ bh_status bh_verify_batch(const uint8_t* vk_bytes, size_t vk_len, const uint8_t*
   fr_to_canonical(acc_y, yw);
   ml.push_back({jac_to_affine(jac_mul(jac_from_affine(vk.alpha_g1), yw, 4)), vk.beta_g2});
   *valid = pairing_product_is_one(ml) ? 1 : 0;
+  return BH_OK;
+}
+
+// bh_verify_batch with the per-proof work on the device: Proof::read of the k proofs
+// (proofs_dev.hip), Q_i = z_i A_i (varbase.hip), acc_Delta = sum z_i C_i (the multiexp, on the same
+// device scalars) and f = prod f(Q_i, B_i) (pairing_dev.hip).  The k (l + 1) Fr products of
+// acc_Gamma, Psi, acc_Y alpha, the three remaining Miller loops and the one final exponentiation
+// stay on the host, as above.
+// Where the reference pairs z A with -B, neither B nor Q is negated here: the three accumulated G1
+// points are, so the product below is the inverse of bh_verify_batch's, and it is one exactly when
+// that is.
+// Errors in bh_verify_batch's order: the verifying key and the input count first; then one walk over
+// j = 0 .. k-1 in the host's order -- z_j (>= r or zero), proof j (the decode's status word: A, B,
+// C), inputs j (>= r) -- whose first failure is returned.
+bh_status bh_verify_batch_device(bh_ctx* ctx, const uint8_t* vk_bytes, size_t vk_len, const uint8_t* proofs,
+                                 const uint64_t* inputs, size_t num_inputs, size_t k, const uint64_t* z, int* valid) {
+  if (!ctx || !vk_bytes || !valid || (k && (!proofs || !z)) || (k && num_inputs && !inputs))
+    return BH_ERR_INVALID_ARGUMENT;
+  *valid = 0;
+  Vk vk;
+  bh_status s = vk_read(vk_bytes, vk_len, &vk);
+  if (s) return s;
+  if (num_inputs + 1 != vk.ic.size()) return BH_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  BH_TRY_HIP(hipSetDevice(ctx->device));
+  if ((s = scratch_check(ctx))) return s;
+  bh_srs pa, pb, pc;
+  std::vector<uint32_t> st;
+  if ((s = proofs_decode_device(ctx, proofs, k, &st, &pa, &pb, &pc))) return s;
+  std::vector<Fr> acc_gamma(vk.ic.size(), Fr::zero());
+  Fr acc_y = Fr::zero();
+  int nbits = 1;
+  for (size_t j = 0; j < k; j++) {
+    const uint64_t* zj = z + 4 * j;
+    if (!canonical_ok(zj) || scalar_is_zero(zj)) return BH_ERR_INVALID_ARGUMENT;
+    if (st[j]) return (bh_status)st[j];
+    const Fr zf = fr_from_canonical(zj);
+    nbits = std::max(nbits, scalar_bits(zj));
+    acc_gamma[0] = add(acc_gamma[0], zf);
+    for (size_t i = 0; i < num_inputs; i++) {
+      const uint64_t* ai = inputs + 4 * (j * num_inputs + i);
+      if (!canonical_ok(ai)) return BH_ERR_INVALID_ARGUMENT;
+      acc_gamma[i + 1] = add(acc_gamma[i + 1], mul(zf, fr_from_canonical(ai)));
+    }
+    acc_y = add(acc_y, zf);
+  }
+  Fp12 f = f12_one();
+  Jac<Fp> acc_delta = jac_identity<Fp>();
+  if (k) {
+    DevBuf d_z;
+    if ((s = varbase_upload_scalars(ctx, z, k, nbits, &d_z))) return s;
+    bh_srs q;
+    if ((s = varbase_mul(ctx, &pa, d_z.as<uint32_t>(), 8, nbits, &q))) return s;
+    if ((s = msm_device<G1Host>(ctx, &pc, 0, d_z.as<uint32_t>(), k, nullptr, &acc_delta, nullptr))) return s;
+    s = miller_product_device(ctx, &q, 0, &pb, 0, k, 0, &f);
+    // a zero denominator: no subgroup-checked B causes one, but the verdict must not rest on that
+    if (s == BH_ERR_PAIRING_DEGENERATE)
+      return bh_verify_batch(vk_bytes, vk_len, proofs, inputs, num_inputs, k, z, valid);
+    if (s) return s;
+  }
+  Jac<Fp> psi = jac_identity<Fp>();
+  for (size_t i = 0; i < vk.ic.size(); i++) {
+    uint64_t w[4];
+    fr_to_canonical(acc_gamma[i], w);
+    psi = jac_add(psi, jac_mul(jac_from_affine(vk.ic[i]), w, 4));
+  }
+  uint64_t yw[4];
+  fr_to_canonical(acc_y, yw);
+  const std::vector<Pair> rest = {{neg_pt(jac_to_affine(acc_delta)), vk.delta_g2},
+                                  {neg_pt(jac_to_affine(psi)), vk.gamma_g2},
+                                  {neg_pt(jac_to_affine(jac_mul(jac_from_affine(vk.alpha_g1), yw, 4))), vk.beta_g2}};
+  f = f12_mul(f, multi_miller_loop(rest));
+  *valid = f12_is_one(final_exponentiation(f)) ? 1 : 0;
   return BH_OK;
 }
 

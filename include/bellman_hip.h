@@ -295,7 +295,8 @@ bh_status bh_vk_write(const bh_params* p, uint8_t* out, size_t cap, size_t* writ
  * each, without the implicit ONE.  *valid = 1 iff the proof(s) verify; the status is non-zero only for
  * malformed data (num_inputs + 1 != ic length: BH_ERR_INVALID_ARGUMENT, the reference's
  * VerificationError::InvalidVerifyingKey).  Batch: k proofs, inputs k * num_inputs * 4 words, and the
- * caller's random nonzero scalars z (k * 4 canonical words; the reference draws them from a CryptoRng). */
+ * caller's random nonzero scalars z (k * 4 canonical words; the reference draws them from a CryptoRng).
+ * bh_verify_batch_device, further down, gives the same answers with the per-proof work on a device. */
 bh_status bh_verify_proof(const uint8_t* vk, size_t vk_len, const uint8_t* proof, const uint64_t* inputs,
                           size_t num_inputs, int* valid);
 bh_status bh_verify_batch(const uint8_t* vk, size_t vk_len, const uint8_t* proofs, const uint64_t* inputs,
@@ -570,6 +571,32 @@ int bh_mpc_last_miller_device(void);
 bh_status bh_miller_product(bh_ctx* ctx, const bh_srs* g1, size_t off1, const bh_srs* g2, size_t off2, size_t n,
                             uint8_t out[576]);
 bh_status bh_final_exponentiation(const uint8_t f[576], uint8_t out[576]);
+
+/* ---- batch verification on the device (verifier/batch.rs:95-169).
+ * bh_verify_batch_device: for every input the status and *valid of bh_verify_batch, with the
+ * per-proof work on the context's device: Proof::read of the k proofs (bh_proofs_decode's kernels),
+ * z_i A_i, sum z_i C_i and the product of the k Miller values f(z_i A_i, B_i).  The Fr sums over the
+ * public inputs, the three remaining Miller loops and the one final exponentiation stay on the host.
+ * Where the reference pairs z A with -B, neither is negated here: the three accumulated G1 points
+ * are, which inverts the whole product and leaves the verdict unchanged.  Errors in the host's
+ * order: the verifying key and the input count; then, walking j = 0 .. k-1, the first of z_j (>= r
+ * or zero: BH_ERR_INVALID_ARGUMENT), proof j (A, B, C) and proof j's inputs (>= r).  k = 0 is valid.
+ * There is no size switch inside: the caller chooses between the two functions.  Should the device
+ * product report BH_ERR_PAIRING_DEGENERATE (no subgroup-checked B causes that), the whole batch runs
+ * through bh_verify_batch and its answer is returned. */
+bh_status bh_verify_batch_device(bh_ctx* ctx, const uint8_t* vk, size_t vk_len, const uint8_t* proofs,
+                                 const uint64_t* inputs, size_t num_inputs, size_t k, const uint64_t* z,
+                                 int* valid);
+/* Proof::read of k proofs (192 bytes each: compressed A, B, C) on the device, each point as the host
+ * verifier decodes it: compression flag clear, infinity flag set, a coordinate >= p (the three flag
+ * bits are masked on a point's first 48 bytes only), x^3 + b not a square: BH_ERR_INVALID_ENCODING;
+ * [r]P != O: BH_ERR_NOT_IN_SUBGROUP.  status[j] (k words, may be NULL) = BH_OK or the error of
+ * proof j's first failing point in the order A, B, C.  All zero: *a, *b, *c are new bh_srs of k
+ * points (G1, G2, G1; B as encoded, not negated), to be freed by the caller.  Otherwise they are
+ * NULL and the call returns the status of the lowest failing j.  k = 0: BH_OK and three empty
+ * vectors. */
+bh_status bh_proofs_decode(bh_ctx* ctx, const uint8_t* proofs, size_t k, uint32_t* status, bh_srs** a, bh_srs** b,
+                           bh_srs** c);
 
 /* Parameters::write of device-resident params (for parity tests; host copy). */
 bh_status bh_params_write(const bh_params* p, uint8_t* out, size_t cap, size_t* written);
