@@ -172,6 +172,9 @@ def _load():
         "bh_r1cs_eval": (I, [P, P, P, P, P, P]),
         "bh_generate_parameters": (I, [P, P, P, P, P, P, P, P]),
         "bh_chain_r1cs": (I, [P, S, U64, P]),
+        "bh_r1cs_witness": (I, [P, P, P, P, P, P]),
+        "bh_witness_sizes": (I, [P, P]),
+        "bh_witness_read": (I, [P, P, P, P, P, P, P, P, P]),
         "bh_srs_mul_each": (I, [P, P, P, S, P]),
         "bh_srs_mul_each_bounded": (I, [P, P, P, S, I, P]),
         "bh_srs_mul_powers": (I, [P, P, P, P, I, P]),
@@ -231,7 +234,7 @@ EXPORTED_SYMBOLS = [
     "bh_mpc_common_initial", "bh_mpc_common_contribute", "bh_mpc_common_verify", "bh_mpc_common_h_basis",
     "bh_mpc_common_len", "bh_mpc_uncommon_initial", "bh_mpc_uncommon_contribute", "bh_mpc_uncommon_verify",
     "bh_mpc_last_miller_ms", "bh_mpc_last_miller_device", "bh_miller_product", "bh_final_exponentiation",
-    "bh_verify_batch_device", "bh_proofs_decode",
+    "bh_verify_batch_device", "bh_proofs_decode", "bh_r1cs_witness", "bh_witness_sizes", "bh_witness_read",
 ] + [f"bh_mpc_{kind}{who}_{op}" for kind in ("common", "uncommon") for who in ("", "_contrib")
      for op in ("free", "vector", "point", "write", "read")]
 BH_VEC_H, BH_VEC_L, BH_VEC_A, BH_VEC_B_G1, BH_VEC_B_G2 = range(5)
@@ -1108,6 +1111,55 @@ class ProvingAssignment:
         self.c.append(self._eval(lc(z()), None, None))
 
 
+class AssignmentOnly:
+    """A ConstraintSystem that records what alloc / alloc_input are given and nothing else: the
+    host's whole share of ProvingAssignment (prover.rs:55-97) once a, b, c and the density maps are
+    computed on the device from a resident R1CS (bh_r1cs_witness)."""
+
+    def __init__(self):
+        self.input_assignment, self.aux_assignment = [], []
+
+    @staticmethod
+    def one():
+        return ONE
+
+    def namespace(self, name):
+        return self
+
+    def alloc(self, name, f):
+        v = f()
+        if v is None:
+            raise AssignmentMissing()
+        self.aux_assignment.append(int(v) % R_MODULUS)
+        return Variable("aux", len(self.aux_assignment) - 1)
+
+    def alloc_input(self, name, f):
+        v = f()
+        if v is None:
+            raise AssignmentMissing()
+        self.input_assignment.append(int(v) % R_MODULUS)
+        return Variable("input", len(self.input_assignment) - 1)
+
+    def enforce(self, name, la, lb, lc):
+        pass
+
+
+def assign(circuit):
+    """prover.rs:187-200 without the evaluation: ONE, then the circuit's allocations."""
+    p = AssignmentOnly()
+    p.alloc_input("", lambda: 1)
+    circuit.synthesize(p)
+    return p
+
+
+def column_densities(asm):
+    """The three density maps of ProvingAssignment (prover.rs:99-139) from a KeypairAssembly's
+    columns: a variable is dense where the circuit gave it at least one term, whatever the
+    coefficient (eval calls inc before it looks at the coefficient).  -> (a_aux, b_input, b_aux)
+    as lists of bool; the rule bh_r1cs_create applies to its column pointers."""
+    return ([bool(c) for c in asm.at_aux], [bool(c) for c in asm.bt_inputs], [bool(c) for c in asm.bt_aux])
+
+
 def synthesize(circuit):
     """prover.rs:187-204"""
     p = ProvingAssignment()
@@ -1143,6 +1195,55 @@ class Witness:
         ps = seed + 1 if preimage_seed is None else preimage_seed
         _check(_lib.bh_chain_witness_preimage(ctx.h, rounds, seed, ps, ctypes.byref(h)), "bh_chain_witness")
         return cls(ctx, h, 2 * rounds + 2)
+
+    @classmethod
+    def from_r1cs(cls, ctx, r1cs, inputs, aux, check=False):
+        """a, b, c and the density maps computed on the device from the resident matrices
+        (bh_r1cs_witness).  inputs / aux: ints, or (n,4) uint64 Montgomery arrays as
+        chain_assignment returns them; inputs[0] is ONE.  check=True: -> (witness, the first
+        unsatisfied constraint's index or None)."""
+        sz = r1cs.sizes()
+        arrs = [x if isinstance(x, np.ndarray) else fr_to_mont(x) for x in (inputs, aux)]
+        arrs = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in arrs]
+        if (arrs[0].shape[0], arrs[1].shape[0]) != (sz["inputs"], sz["aux"]):
+            raise ValueError(f"the circuit has {sz['inputs']} inputs and {sz['aux']} aux variables")
+        h = ctypes.c_void_p()
+        first = ctypes.c_size_t()
+        _check(_lib.bh_r1cs_witness(ctx.h, r1cs.h, _ptr(arrs[0]), _ptr(arrs[1]),
+                                    ctypes.byref(first) if check else None, ctypes.byref(h)), "bh_r1cs_witness")
+        w = cls(ctx, h, sz["constraints"])
+        if not check:
+            return w
+        return w, (None if first.value == ctypes.c_size_t(-1).value else first.value)
+
+    def sizes(self):
+        out = (ctypes.c_size_t * 4)()
+        _check(_lib.bh_witness_sizes(self.h, out))
+        return dict(zip(["constraints", "m", "inputs", "aux"], list(out)))
+
+    def read(self, raw=False):
+        """What the witness holds (bh_witness_read): a, b, c as m ints each, inputs and aux as
+        ints, the three density maps as lists of bool.  raw=True: the arrays as the library wrote
+        them instead, (n,4) uint64 Montgomery (reduced) and uint64 density words, for comparing large
+        witnesses without a Python integer per element."""
+        sz = self.sizes()
+        m, ni, na = sz["m"], sz["inputs"], sz["aux"]
+        vec = {k: np.zeros((n, 4), dtype=np.uint64) for k, n in (("a", m), ("b", m), ("c", m), ("inputs", ni),
+                                                                  ("aux", na))}
+        dens = {k: np.zeros(max(1, (n + 63) // 64), dtype=np.uint64)
+                for k, n in (("a_aux_density", na), ("b_input_density", ni), ("b_aux_density", na))}
+        _check(_lib.bh_witness_read(self.h, *[_ptr(vec[k]) for k in ("a", "b", "c", "inputs", "aux")],
+                                    *[_ptr(dens[k]) for k in ("a_aux_density", "b_input_density", "b_aux_density")]),
+               "bh_witness_read")
+        out = dict(sz)
+        if raw:
+            out.update(vec)
+            out.update(dens)
+            return out
+        out.update({k: fr_from_mont(v) for k, v in vec.items()})
+        for k, n in (("a_aux_density", na), ("b_input_density", ni), ("b_aux_density", na)):
+            out[k] = [bool((int(dens[k][i >> 6]) >> (i & 63)) & 1) for i in range(n)]
+        return out
 
     def __del__(self):
         try:
@@ -1235,6 +1336,15 @@ def create_proof(ctx, circuit, params, r, s):
     """prover.rs:175-350: synthesize on the host, prove on the device."""
     p = synthesize(circuit)
     w = Witness.from_assignment(ctx, p)
+    return prove_witness(ctx, params, w, r, s)
+
+
+def create_proof_r1cs(ctx, r1cs, circuit, params, r, s):
+    """create_proof (prover.rs:175-350) with only the allocations on the host: a, b, c and the
+    density maps come from the circuit's resident matrices (R1CS.from_assembly of the same
+    circuit, the handle the parameters were generated from)."""
+    p = assign(circuit)
+    w = Witness.from_r1cs(ctx, r1cs, p.input_assignment, p.aux_assignment)
     return prove_witness(ctx, params, w, r, s)
 
 

@@ -465,6 +465,16 @@ bh_status download_points(const bh_srs& v, size_t n, std::vector<typename G::Aff
 bh_status upload_fr(bh_ctx* ctx, const uint64_t* host, size_t n, size_t padded, uint32_t* dst);
 // the same through the context's pinned staging ring, enqueued on st (caller holds ctx->mu)
 bh_status upload_fr_staged(bh_ctx* ctx, const uint64_t* host, size_t n, size_t padded, uint32_t* dst, hipStream_t st);
+// prover.hip, shared by every producer of a resident witness (bh_witness_upload, bh_prove,
+// bh_r1cs_witness; caller holds ctx->mu).  witness_host: sizes, host copies of the density maps,
+// their prefix counts and totals, h_inputs, and the device buffers (nothing is copied yet; a, b, c
+// are the caller's to check).  witness_density_upload: the host density words -> w->dens on st.
+// witness_index_maps: idx3 from w->dens, stream-ordered on st behind that upload.
+bh_status witness_host(bh_ctx* ctx, bh_witness* w, size_t nc, const uint64_t* inputs, size_t ni, const uint64_t* aux,
+                       size_t na, const uint64_t* a_aux_density, const uint64_t* b_input_density,
+                       const uint64_t* b_aux_density);
+bh_status witness_density_upload(bh_witness* w, hipStream_t st);
+bh_status witness_index_maps(bh_ctx* ctx, bh_witness* w, hipStream_t st);
 bh::HostPool& ctx_pool(bh_ctx* ctx);
 // bls12_381 Montgomery (R = 2^256) -> device Montgomery (R = 2^261) multiplier for launch_fr_convert
 FrConst fr_to_dev_const();

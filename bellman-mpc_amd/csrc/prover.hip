@@ -101,11 +101,15 @@ inline size_t popcount_words(const std::vector<uint64_t>& w, size_t nbits) {
 // prefix counts, device buffers; witness_device: the staged copies and format conversions on
 // stream st, in the order the prover needs them -- density maps, inputs, aux (then up stage
 // 1: every multiexp's sort can start), a, b, c (stage 2: the H block can start).
-bh_status witness_host(bh_ctx* ctx, bh_witness* w, const uint64_t* a, const uint64_t* b, const uint64_t* c,
-                       size_t nc, const uint64_t* inputs, size_t ni, const uint64_t* aux, size_t na,
-                       const uint64_t* a_aux_density, const uint64_t* b_input_density,
+// witness_host, witness_density_upload and witness_index_maps are shared with bh_r1cs_witness
+// (api_internal.h), which has no a, b, c to pass: those three pointers are the caller's to check.
+}  // namespace
+
+namespace bh {
+bh_status witness_host(bh_ctx* ctx, bh_witness* w, size_t nc, const uint64_t* inputs, size_t ni, const uint64_t* aux,
+                       size_t na, const uint64_t* a_aux_density, const uint64_t* b_input_density,
                        const uint64_t* b_aux_density) {
-  if ((nc && (!a || !b || !c)) || (ni && !inputs) || (na && !aux)) return BH_ERR_INVALID_ARGUMENT;
+  if ((ni && !inputs) || (na && !aux)) return BH_ERR_INVALID_ARGUMENT;
   if ((na && (!a_aux_density || !b_aux_density)) || (ni && !b_input_density)) return BH_ERR_INVALID_ARGUMENT;
   size_t m;
   uint32_t L;
@@ -143,6 +147,9 @@ bh_status witness_host(bh_ctx* ctx, bh_witness* w, const uint64_t* a, const uint
   BH_TRY_HIP(w->dens.alloc(std::max<size_t>(tw, 1) * 8));
   return BH_OK;
 }
+}  // namespace bh
+
+namespace {
 
 // Caller (pageable) bytes -> device on the copy stream st: the pinned staging ring (memcpy
 // workers + DMA).  (One hipMemcpyAsync from the pageable buffer -- the runtime's own staging, 56
@@ -152,8 +159,11 @@ hipError_t upload_host(bh_ctx* ctx, void* dst, const void* src, size_t bytes, hi
   return ctx->ring.copy(ctx_pool(ctx), dst, src, bytes, st);
 }
 
-bh_status witness_device_impl(bh_ctx* ctx, bh_witness* w, const uint64_t* a, const uint64_t* b, const uint64_t* c,
-                              const uint64_t* inputs, const uint64_t* aux, hipStream_t st, UploadSync* up) {
+}  // namespace
+
+namespace bh {
+// the witness's host density words -> its device words (a_aux | b_input | b_aux), enqueued on st
+bh_status witness_density_upload(bh_witness* w, hipStream_t st) {
   uint64_t* d = w->dens.as<uint64_t>();
   if (w->a_aux_words)
     BH_TRY_HIP(hipMemcpyAsync(d, w->a_aux_density.data(), w->a_aux_words * 8, hipMemcpyHostToDevice, st));
@@ -163,6 +173,16 @@ bh_status witness_device_impl(bh_ctx* ctx, bh_witness* w, const uint64_t* a, con
   if (w->b_aux_words)
     BH_TRY_HIP(hipMemcpyAsync(d + w->a_aux_words + w->b_in_words, w->b_aux_density.data(), w->b_aux_words * 8,
                               hipMemcpyHostToDevice, st));
+  return BH_OK;
+}
+}  // namespace bh
+
+namespace {
+
+bh_status witness_device_impl(bh_ctx* ctx, bh_witness* w, const uint64_t* a, const uint64_t* b, const uint64_t* c,
+                              const uint64_t* inputs, const uint64_t* aux, hipStream_t st, UploadSync* up) {
+  bh_status ds = witness_density_upload(w, st);
+  if (ds) return ds;
   HostPool& pool = ctx_pool(ctx);
   const size_t ni = w->num_inputs, na = w->num_aux, nc = w->num_constraints, m = w->m;
   uint32_t* abc = w->abc.as<uint32_t>();
@@ -205,6 +225,9 @@ bh_status witness_device_impl(bh_ctx* ctx, bh_witness* w, const uint64_t* a, con
   return BH_OK;
 }
 
+}  // namespace
+
+namespace bh {
 // the density index maps of a device-resident witness, once (density_index: a base index per
 // set bit, -1 per clear one), stream-ordered on st after the density words' upload
 bh_status witness_index_maps(bh_ctx* ctx, bh_witness* w, hipStream_t st) {
@@ -223,6 +246,9 @@ bh_status witness_index_maps(bh_ctx* ctx, bh_witness* w, hipStream_t st) {
   w->idx_ready = true;
   return BH_OK;
 }
+}  // namespace bh
+
+namespace {
 
 // always leaves `up` in a final stage (2, or -1 with the status) so that no waiter hangs
 bh_status witness_device(bh_ctx* ctx, bh_witness* w, const uint64_t* a, const uint64_t* b, const uint64_t* c,
@@ -300,8 +326,8 @@ bh_status bh_witness_upload(bh_ctx* ctx, const uint64_t* a, const uint64_t* b, c
   std::lock_guard<std::mutex> lk(ctx->mu);
   BH_TRY_HIP(hipSetDevice(ctx->device));
   std::unique_ptr<bh_witness> w(new bh_witness());
-  bh_status s = witness_host(ctx, w.get(), a, b, c, nc, inputs, ni, aux, na, a_aux_density, b_input_density,
-                             b_aux_density);
+  if (nc && (!a || !b || !c)) return BH_ERR_INVALID_ARGUMENT;
+  bh_status s = witness_host(ctx, w.get(), nc, inputs, ni, aux, na, a_aux_density, b_input_density, b_aux_density);
   if (s) return s;
   if ((s = witness_device(ctx, w.get(), a, b, c, inputs, aux, ctx->h2d, nullptr))) return s;
   if ((s = witness_index_maps(ctx, w.get(), ctx->h2d))) return s;
@@ -1923,8 +1949,8 @@ bh_status bh_prove(bh_ctx* ctx, const bh_params* params, const uint64_t* a, cons
   // once aux has landed, the H block once a, b, c have (pinned ring + memcpy threads)
   if (!ctx->dropin) ctx->dropin = new bh_witness();
   bh_witness* w = ctx->dropin;
-  bh_status st = witness_host(ctx, w, a, b, c, nc, inputs, ni, aux, na, a_aux_density, b_input_density,
-                              b_aux_density);
+  if (nc && (!a || !b || !c)) return BH_ERR_INVALID_ARGUMENT;
+  bh_status st = witness_host(ctx, w, nc, inputs, ni, aux, na, a_aux_density, b_input_density, b_aux_density);
   if (st) return st;
   UploadSync up;
   struct EvGuard {

@@ -23,6 +23,28 @@ struct bh_r1cs {
   bh::DevBuf seg;           // nseg + 1 u32: first term of each segment, seg[nseg] = terms
   bh::DevBuf colseg;        // ncol + 1 u32: first segment of each column
   bh::DevBuf longcols;      // nlong u32: the columns with more than R1CS_S segments
+  // ProvingAssignment's density maps (prover.rs:99-139): bit i = the circuit put at least one term
+  // into variable i's column of A (aux) / B (inputs, aux).  A function of the column pointers alone
+  // (the appended rows touch only A's input columns, which have no map), so bh_r1cs_create keeps them
+  std::vector<uint64_t> a_aux_density, b_input_density, b_aux_density;
+  // The row view bh_r1cs_witness multiplies with: the same terms listed by row.  Row k * m + i is
+  // constraint i of matrix k (A, B, C), so the products land in a witness's a | b | c buffer as they
+  // are and the rows nc .. m are empty.  Built on the device by the first bh_r1cs_witness of the
+  // handle, under rv.mu, which every call holds to its end (rv.words is per-call state); a handle
+  // that only generates parameters never allocates any of it.  Coefficients are not copied: a row's
+  // entry is the term's index into coeff and its variable, 8 bytes per term.
+  struct RowView {
+    std::mutex mu;
+    bool ready = false;
+    size_t nrows = 0, nseg = 0, nlong = 0;
+    bh::DevBuf term;      // terms u32: index into coeff / row, grouped by row
+    bh::DevBuf var;       // terms u32: that term's variable (inputs, then aux)
+    bh::DevBuf seg;       // nseg + 1 u32: first entry of each row segment, seg[nseg] = terms
+    bh::DevBuf rowseg;    // nrows + 1 u32: first segment of each row
+    bh::DevBuf longrows;  // nlong u32: the rows with more than R1CS_S segments
+    bh::DevBuf words;     // 2 u32: [0] the long rows' counter (build), [1] first unsatisfied row
+  };
+  mutable RowView rv;
 };
 
 namespace bh {

@@ -15,6 +15,18 @@
 // the Lagrange coefficients the resident ifft of the powers, the flags' prefix msm_common.hip's
 // tiled scan, and the points crs.hip's fixed_base_batch.  Field addition is exact, so the order of
 // the partial sums does not matter and nothing here is atomic but the one u32 counter.
+//
+// The prover's side, bh_r1cs_witness: ProvingAssignment's a = A z, b = B z, c = C z (prover.rs:19-53,
+// 99-139) as the same two passes over the ROW view of the matrices, which the first call builds from
+// the column arrays on the device.
+//   k_r1cs_row_keys      per term: its column (a search of the segment starts), hence its matrix and
+//                        variable, its row key = matrix * m + row, and the rows' histogram
+//   k_r1cs_row_scatter   per term: a slot of its row from the row's cursor
+//   k_r1cs_row_segcount / k_r1cs_row_fill   the rows cut into segments as the columns are
+//   k_r1cs_row_segments  pass 1 by rows: partial = sum coeff[term] * z[var]   (eval, prover.rs:19-53)
+//   k_r1cs_unsatisfied   a_i * b_i != c_i -> the least such i (TestConstraintSystem::which_is_unsatisfied)
+// The histogram and the cursors are u32 atomics, so the order of a row's terms differs from build
+// to build.  That changes no result: a row's value is a sum in Fr, and field addition is exact.
 #include <string.h>
 
 #include <algorithm>
@@ -122,7 +134,106 @@ __global__ void __launch_bounds__(256) k_r1cs_compact(const uint32_t* y, const u
   st_canonical(out, pos[j], ld_packed(y, j));
 }
 
+// ---- the row view (r1cs.h: bh_r1cs::RowView)
+// the column of term t: the one j with seg[colseg[j]] <= t < seg[colseg[j + 1]].  Empty columns
+// share their successor's start and are never the answer; seg[colseg[0]] = 0 and
+// seg[colseg[ncol]] = terms bracket every t
+__device__ __forceinline__ uint32_t term_column(const uint32_t* seg, const uint32_t* colseg, uint32_t ncol,
+                                                uint32_t t) {
+  uint32_t lo = 0, hi = ncol;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (seg[colseg[mid]] <= t) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// n: variables, m: domain size (rows per matrix in the view).  row[t] < m was checked at creation
+__global__ void __launch_bounds__(256) k_r1cs_row_keys(const uint32_t* seg, const uint32_t* colseg, uint32_t ncol,
+                                                       const uint32_t* row, uint32_t terms, uint32_t n, uint32_t m,
+                                                       uint32_t* key, uint32_t* var, uint32_t* hist) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= terms) return;
+  const uint32_t col = term_column(seg, colseg, ncol, t);
+  const uint32_t k = col / n;
+  const uint32_t key_t = k * m + row[t];
+  key[t] = key_t;
+  var[t] = col - k * n;
+  atomicAdd(&hist[key_t], 1u);
+}
+
+// cursor: a copy of the rows' first slots; every row hands out exactly its histogram count
+__global__ void __launch_bounds__(256) k_r1cs_row_scatter(const uint32_t* key, const uint32_t* var, uint32_t terms,
+                                                          uint32_t* cursor, uint32_t* out_term, uint32_t* out_var) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= terms) return;
+  const uint32_t p = atomicAdd(&cursor[key[t]], 1u);
+  out_term[p] = t;
+  out_var[p] = var[t];
+}
+
+// cnt[i] = segments of row i, cnt[nrows] = 0 (so that the exclusive scan ends in the total)
+__global__ void __launch_bounds__(256) k_r1cs_row_segcount(const uint32_t* rowptr, uint32_t nrows, uint32_t* cnt) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > nrows) return;
+  cnt[i] = i < nrows ? (rowptr[i + 1] - rowptr[i] + R1CS_S - 1) / R1CS_S : 0u;
+}
+
+// seg: rowseg[nrows] + 1 entries.  A row of more than R1CS_S segments has more than R1CS_S^2 terms,
+// so there are fewer than long_cap = terms / R1CS_S^2 + 1 of them
+__global__ void __launch_bounds__(256) k_r1cs_row_fill(const uint32_t* rowptr, const uint32_t* rowseg, uint32_t nrows,
+                                                       uint32_t* seg, uint32_t* longrows, uint32_t long_cap,
+                                                       uint32_t* nlong) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > nrows) return;
+  const uint32_t s0 = rowseg[i];
+  if (i == nrows) {
+    seg[s0] = rowptr[nrows];
+    return;
+  }
+  const uint32_t cnt = rowseg[i + 1] - s0, t0 = rowptr[i];
+  for (uint32_t s = 0; s < cnt; s++) seg[s0 + s] = t0 + s * R1CS_S;
+  if (cnt > R1CS_S) {
+    const uint32_t q = atomicAdd(nlong, 1u);
+    if (q < long_cap) longrows[q] = i;
+  }
+}
+
+// pass 1 by rows, the indirect counterpart of k_r1cs_segments: entry p of the view is term[p] of
+// the column arrays times variable var[p] of z (packed device Montgomery, < 2r)
+__global__ void __launch_bounds__(256) k_r1cs_row_segments(const uint32_t* coeff, const uint32_t* term,
+                                                           const uint32_t* var, const uint32_t* seg, uint32_t nseg,
+                                                           const uint32_t* z, uint32_t* part) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nseg) return;
+  const uint32_t p0 = seg[k], p1 = seg[k + 1];
+  DFr acc = fe_zero<FrCfg>();
+  for (uint32_t p = p0; p < p1; p++)
+    acc = fr_acc(acc, fe_mul<FrCfg>(ld_packed(coeff, term[p]), ld_packed(z, var[p])));
+  st_packed(part, k, acc);
+}
+
+// abc: a | b | c, m each, < 2r.  a b < 2r and c < 2r: the difference (+ 2r) is < 4r and is reduced
+// to [0, r) before it is compared with zero.  (fe_is_zero's test x == k r is not used here: nine
+// limbs hold 261 bits and 71 r is more, so for Fr it also accepts 71 r - 2^261 = r - (2^261 mod r),
+// the Montgomery form of -1 -- precisely a constraint whose c is too large by one.)
+__global__ void __launch_bounds__(256) k_r1cs_unsatisfied(const uint32_t* abc, uint32_t m, uint32_t nc,
+                                                          uint32_t* first) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nc) return;
+  const DFr ab = fe_mul<FrCfg>(ld_packed(abc, i), ld_packed(abc, (size_t)m + i));
+  const DFr d = fe_sub<FrCfg, 2>(ab, ld_packed(abc, 2 * (size_t)m + i));
+  if (!fe_is_zero_canonical<FrCfg>(fe_csub<FrCfg, 1>(fe_csub<FrCfg, 2>(d)))) atomicMin(first, i);
+}
+
 void r1cs_kernels(std::vector<KernInfo>& v) {
+  v.push_back({"k_r1cs_row_keys", (const void*)k_r1cs_row_keys, 256, 0});
+  v.push_back({"k_r1cs_row_scatter", (const void*)k_r1cs_row_scatter, 256, 0});
+  v.push_back({"k_r1cs_row_segcount", (const void*)k_r1cs_row_segcount, 256, 0});
+  v.push_back({"k_r1cs_row_fill", (const void*)k_r1cs_row_fill, 256, 0});
+  v.push_back({"k_r1cs_row_segments", (const void*)k_r1cs_row_segments, 256, 0});
+  v.push_back({"k_r1cs_unsatisfied", (const void*)k_r1cs_unsatisfied, 256, 0});
   v.push_back({"k_r1cs_powers", (const void*)k_r1cs_powers, 256, 0});
   v.push_back({"k_r1cs_segments", (const void*)k_r1cs_segments, 256, 0});
   v.push_back({"k_r1cs_columns", (const void*)k_r1cs_columns, 256, 0});
@@ -195,6 +306,16 @@ FrConst from_dev_const() {
 
 bool below_r(const uint64_t w[4]) { return !geq_p<4>(w); }
 
+// pass 2: y[j] = the sum of the partials colseg[j] .. colseg[j + 1], for columns or for rows alike
+hipError_t sum_partials(const uint32_t* colseg, size_t ncol, const uint32_t* longcols, size_t nlong,
+                        const uint32_t* d_part, uint32_t* d_y, hipStream_t st) {
+  hipLaunchKernelGGL(k_r1cs_columns, dim3(nb(ncol, 256)), dim3(256), 0, st, colseg, (uint32_t)ncol, d_part, d_y);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (nlong) hipLaunchKernelGGL(k_r1cs_long, dim3((unsigned)nlong), dim3(64), 0, st, longcols, colseg, d_part, d_y);
+  return hipGetLastError();
+}
+
 // the QAP evaluation of every column against d_x (m packed device-Montgomery Fr): d_y receives
 // ncol values, d_part is nseg values of scratch.  Enqueued on st.
 hipError_t qap_eval(const bh_r1cs* r, const uint32_t* d_x, uint32_t* d_part, uint32_t* d_y, hipStream_t st) {
@@ -203,14 +324,7 @@ hipError_t qap_eval(const bh_r1cs* r, const uint32_t* d_x, uint32_t* d_part, uin
                        r->row.as<uint32_t>(), r->seg.as<uint32_t>(), (uint32_t)r->nseg, d_x, d_part);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_r1cs_columns, dim3(nb(r->ncol, 256)), dim3(256), 0, st, r->colseg.as<uint32_t>(),
-                     (uint32_t)r->ncol, d_part, d_y);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  if (r->nlong)
-    hipLaunchKernelGGL(k_r1cs_long, dim3((unsigned)r->nlong), dim3(64), 0, st, r->longcols.as<uint32_t>(),
-                       r->colseg.as<uint32_t>(), d_part, d_y);
-  return hipGetLastError();
+  return sum_partials(r->colseg.as<uint32_t>(), r->ncol, r->longcols.as<uint32_t>(), r->nlong, d_part, d_y, st);
 }
 
 struct Matrix {
@@ -261,6 +375,17 @@ bh_status bh_r1cs_create(bh_ctx* ctx, size_t num_inputs, size_t num_aux, size_t 
   r->nnz[2] = c_ptr[n];
   r->terms = terms;
   r->ncol = 3 * n;
+  // eval (prover.rs:19-53) calls inc for every term before it looks at the coefficient: a variable is
+  // dense in a matrix exactly when the circuit's own column is not empty
+  auto dense = [](const uint64_t* ptr, size_t first, size_t count) {
+    std::vector<uint64_t> w((count + 63) / 64, 0);
+    for (size_t i = 0; i < count; i++)
+      if (ptr[first + i + 1] > ptr[first + i]) w[i >> 6] |= 1ull << (i & 63);
+    return w;
+  };
+  r->a_aux_density = dense(a_ptr, num_inputs, num_aux);
+  r->b_input_density = dense(b_ptr, 0, num_inputs);
+  r->b_aux_density = dense(b_ptr, num_inputs, num_aux);
   // the concatenated term arrays and the segment scheme
   std::vector<uint64_t> hc(terms * 4);
   std::vector<uint32_t> hr(terms), hseg, hcol(r->ncol + 1), hlong;
@@ -473,6 +598,188 @@ bh_status bh_generate_parameters(bh_ctx* ctx, const bh_r1cs* r, const uint64_t a
   p->delta_g1 = g1mul(delta_w);
   p->delta_g2 = g2mul(delta_w);
   *out = p.release();
+  return BH_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The row view of r (r1cs.h), built once per handle on st.  Caller holds ctx->mu and r->rv.mu.
+// Scratch while it builds: 8 bytes per term (keys, variables) and three words per row; kept: 8
+// bytes per term, one word per row and per row segment.
+bh_status row_view(const bh_r1cs* r, hipStream_t st) {
+  bh_r1cs::RowView& rv = r->rv;
+  if (rv.ready) return BH_OK;
+  const size_t terms = r->terms, nrows = 3 * r->m, n = r->ni + r->na;
+  if (nrows + 1 > 0xffffffffull) return BH_ERR_INVALID_ARGUMENT;  // u32 row keys
+  const size_t long_cap = terms / ((size_t)R1CS_S * R1CS_S) + 1;
+  DevBuf d_key, d_var, d_hist, d_rowptr, d_cursor, d_scan;
+  BH_TRY_HIP(d_key.alloc(terms * 4));
+  BH_TRY_HIP(d_var.alloc(terms * 4));
+  BH_TRY_HIP(d_hist.alloc((nrows + 1) * 4));
+  BH_TRY_HIP(d_rowptr.alloc((nrows + 1) * 4));
+  BH_TRY_HIP(d_cursor.alloc((nrows + 1) * 4));
+  BH_TRY_HIP(d_scan.alloc(scan_scratch_words(nrows + 1) * 4 + 64));
+  BH_TRY_HIP(rv.term.alloc(terms * 4));
+  BH_TRY_HIP(rv.var.alloc(terms * 4));
+  BH_TRY_HIP(rv.rowseg.alloc((nrows + 1) * 4));
+  BH_TRY_HIP(rv.longrows.alloc(long_cap * 4));
+  BH_TRY_HIP(rv.words.alloc(2 * 4));
+  uint32_t* hist = d_hist.as<uint32_t>();
+  uint32_t* rowptr = d_rowptr.as<uint32_t>();
+  // rows' histogram -> first slots -> scatter through per-row cursors
+  BH_TRY_HIP(hipMemsetAsync(hist, 0, (nrows + 1) * 4, st));
+  BH_TRY_HIP(hipMemsetAsync(rv.words.p, 0, 2 * 4, st));
+  hipLaunchKernelGGL(k_r1cs_row_keys, dim3(nb(terms, 256)), dim3(256), 0, st, r->seg.as<uint32_t>(),
+                     r->colseg.as<uint32_t>(), (uint32_t)r->ncol, r->row.as<uint32_t>(), (uint32_t)terms, (uint32_t)n,
+                     (uint32_t)r->m, d_key.as<uint32_t>(), d_var.as<uint32_t>(), hist);
+  BH_TRY_HIP(hipGetLastError());
+  exclusive_scan(hist, rowptr, nrows + 1, d_scan.as<uint32_t>(), st);
+  BH_TRY_HIP(hipGetLastError());
+  BH_TRY_HIP(hipMemcpyAsync(d_cursor.p, rowptr, (nrows + 1) * 4, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(k_r1cs_row_scatter, dim3(nb(terms, 256)), dim3(256), 0, st, d_key.as<uint32_t>(),
+                     d_var.as<uint32_t>(), (uint32_t)terms, d_cursor.as<uint32_t>(), rv.term.as<uint32_t>(),
+                     rv.var.as<uint32_t>());
+  BH_TRY_HIP(hipGetLastError());
+  // segments per row (the histogram's buffer is free again), their scan, then the fill
+  hipLaunchKernelGGL(k_r1cs_row_segcount, dim3(nb(nrows + 1, 256)), dim3(256), 0, st, rowptr, (uint32_t)nrows, hist);
+  BH_TRY_HIP(hipGetLastError());
+  exclusive_scan(hist, rv.rowseg.as<uint32_t>(), nrows + 1, d_scan.as<uint32_t>(), st);
+  BH_TRY_HIP(hipGetLastError());
+  uint32_t nseg = 0, nlong = 0;
+  BH_TRY_HIP(hipMemcpyAsync(&nseg, rv.rowseg.as<uint32_t>() + nrows, 4, hipMemcpyDeviceToHost, st));
+  BH_TRY_HIP(hipStreamSynchronize(st));  // the segment array is sized by the count
+  BH_TRY_HIP(rv.seg.alloc(((size_t)nseg + 1) * 4));
+  hipLaunchKernelGGL(k_r1cs_row_fill, dim3(nb(nrows + 1, 256)), dim3(256), 0, st, rowptr, rv.rowseg.as<uint32_t>(),
+                     (uint32_t)nrows, rv.seg.as<uint32_t>(), rv.longrows.as<uint32_t>(), (uint32_t)long_cap,
+                     rv.words.as<uint32_t>());
+  BH_TRY_HIP(hipGetLastError());
+  BH_TRY_HIP(hipMemcpyAsync(&nlong, rv.words.p, 4, hipMemcpyDeviceToHost, st));
+  BH_TRY_HIP(hipStreamSynchronize(st));  // the scratch is freed on return
+  if (nlong > long_cap) return BH_ERR_HIP;  // (cannot happen: see k_r1cs_row_fill)
+  rv.nrows = nrows;
+  rv.nseg = nseg;
+  rv.nlong = nlong;
+  rv.ready = true;
+  return BH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+bh_status bh_r1cs_witness(bh_ctx* ctx, const bh_r1cs* r, const uint64_t* input_assignment,
+                          const uint64_t* aux_assignment, size_t* first_unsatisfied, bh_witness** out) {
+  if (!ctx || !r || !out || !input_assignment || (r->na && !aux_assignment) || r->device != ctx->device)
+    return BH_ERR_INVALID_ARGUMENT;
+  const size_t ni = r->ni, na = r->na, n = ni + na, nc = r->nc, m = r->m;
+  for (size_t i = 0; i < ni; i++)
+    if (!below_r(input_assignment + 4 * i)) return BH_ERR_INVALID_ARGUMENT;
+  for (size_t i = 0; i < na; i++)
+    if (!below_r(aux_assignment + 4 * i)) return BH_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  BH_TRY_HIP(hipSetDevice(ctx->device));
+  bh_status s = scratch_check(ctx);
+  if (s) return s;
+  // one stream for all of it, as bh_witness_upload: the copy stream, synchronised before returning
+  hipStream_t st = ctx->h2d;
+  std::lock_guard<std::mutex> rlk(r->rv.mu);
+  if ((s = row_view(r, st))) return s;
+  const bh_r1cs::RowView& rv = r->rv;
+  std::unique_ptr<bh_witness> w(new bh_witness());
+  if ((s = witness_host(ctx, w.get(), nc, input_assignment, ni, aux_assignment, na, r->a_aux_density.data(),
+                        r->b_input_density.data(), r->b_aux_density.data())))
+    return s;
+  if (w->m != m) return BH_ERR_INVALID_ARGUMENT;
+  w->raw = false;
+  if ((s = witness_density_upload(w.get(), st))) return s;
+  // z = [inputs, aux] in device Montgomery for the product; the witness's own copies canonical, as
+  // the multiexps read them (scalars_prepare, like bh_witness_upload).  The context's staging
+  // buffers are free under ctx->mu: the partial sums and z need nothing of their own
+  BH_TRY_HIP(ctx->staging.alloc(std::max<size_t>(rv.nseg, 1) * 32));
+  BH_TRY_HIP(ctx->staging2.alloc(n * 32));
+  uint32_t* d_part = ctx->staging.as<uint32_t>();
+  uint32_t* d_z = ctx->staging2.as<uint32_t>();
+  HostPool& pool = ctx_pool(ctx);
+  BH_TRY_HIP(ctx->ring.copy(pool, w->inputs.p, input_assignment, ni * 32, st));
+  launch_fr_convert(w->inputs.as<uint32_t>(), d_z, ni, fr_to_dev_const(), 0, st);
+  BH_TRY_HIP(hipGetLastError());
+  BH_TRY_HIP(scalars_prepare(w->inputs.as<uint32_t>(), w->inputs.as<uint32_t>(), ni, 1, 0, st));
+  if (na) {
+    BH_TRY_HIP(ctx->ring.copy(pool, w->aux.p, aux_assignment, na * 32, st));
+    launch_fr_convert(w->aux.as<uint32_t>(), d_z + ni * 8, na, fr_to_dev_const(), 0, st);
+    BH_TRY_HIP(hipGetLastError());
+    BH_TRY_HIP(scalars_prepare(w->aux.as<uint32_t>(), w->aux.as<uint32_t>(), na, 1, 0, st));
+  }
+  // a | b | c = the rows' sums, straight into the witness: every one of the 3 m rows is written,
+  // the empty ones (nc .. m of each matrix) with zero
+  uint32_t* abc = w->abc.as<uint32_t>();
+  if (rv.nseg)
+    hipLaunchKernelGGL(k_r1cs_row_segments, dim3(nb(rv.nseg, 256)), dim3(256), 0, st, r->coeff.as<uint32_t>(),
+                       rv.term.as<uint32_t>(), rv.var.as<uint32_t>(), rv.seg.as<uint32_t>(), (uint32_t)rv.nseg, d_z,
+                       d_part);
+  BH_TRY_HIP(hipGetLastError());
+  BH_TRY_HIP(sum_partials(rv.rowseg.as<uint32_t>(), rv.nrows, rv.longrows.as<uint32_t>(), rv.nlong, d_part, abc, st));
+  uint32_t first = 0xffffffffu;
+  if (first_unsatisfied) {
+    uint32_t* d_first = rv.words.as<uint32_t>() + 1;
+    BH_TRY_HIP(hipMemsetAsync(d_first, 0xff, 4, st));
+    hipLaunchKernelGGL(k_r1cs_unsatisfied, dim3(nb(nc, 256)), dim3(256), 0, st, abc, (uint32_t)m, (uint32_t)nc,
+                       d_first);
+    BH_TRY_HIP(hipGetLastError());
+    BH_TRY_HIP(hipMemcpyAsync(&first, d_first, 4, hipMemcpyDeviceToHost, st));
+  }
+  if ((s = witness_index_maps(ctx, w.get(), st))) return s;
+  BH_TRY_HIP(hipStreamSynchronize(st));
+  if (first_unsatisfied) *first_unsatisfied = first == 0xffffffffu ? SIZE_MAX : (size_t)first;
+  *out = w.release();
+  return BH_OK;
+}
+
+bh_status bh_witness_sizes(const bh_witness* w, size_t sizes[4]) {
+  if (!w || !sizes) return BH_ERR_INVALID_ARGUMENT;
+  sizes[0] = w->num_constraints;
+  sizes[1] = w->m;
+  sizes[2] = w->num_inputs;
+  sizes[3] = w->num_aux;
+  return BH_OK;
+}
+
+bh_status bh_witness_read(const bh_witness* w, uint64_t* a, uint64_t* b, uint64_t* c, uint64_t* inputs,
+                          uint64_t* aux, uint64_t* a_aux_density, uint64_t* b_input_density,
+                          uint64_t* b_aux_density) {
+  if (!w || !w->ctx || w->raw) return BH_ERR_INVALID_ARGUMENT;  // (raw: bh_prove's own, never handed out)
+  bh_ctx* ctx = w->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  BH_TRY_HIP(hipSetDevice(ctx->device));
+  const size_t m = w->m, ni = w->num_inputs, na = w->num_aux;
+  hipStream_t st = ctx->stream;
+  // the witness is left as it is: each vector is converted into the context's staging buffer
+  BH_TRY_HIP(ctx->staging.alloc(std::max({m, ni, na, (size_t)1}) * 32));
+  uint32_t* d_tmp = ctx->staging.as<uint32_t>();
+  uint64_t* vecs[3] = {a, b, c};
+  for (int v = 0; v < 3; v++) {
+    if (!vecs[v]) continue;
+    launch_fr_convert(w->abc.as<uint32_t>() + (size_t)v * m * 8, d_tmp, m, from_dev_const(), 1, st);
+    BH_TRY_HIP(hipGetLastError());
+    BH_TRY_HIP(hipMemcpyAsync(vecs[v], d_tmp, m * 32, hipMemcpyDeviceToHost, st));
+    BH_TRY_HIP(hipStreamSynchronize(st));
+  }
+  // canonical x -> bls12_381 Montgomery x 2^256: launch_fr_convert's x * k * 2^-261 with k = 2^517
+  Fr one = Fr::one();
+  const FrConst to_mont = dev_limbs(fr_from_canonical(one.v));
+  const struct { uint64_t* host; const DevBuf& dev; size_t n; } sc[2] = {{inputs, w->inputs, ni}, {aux, w->aux, na}};
+  for (const auto& x : sc) {
+    if (!x.host || !x.n) continue;
+    launch_fr_convert(x.dev.as<uint32_t>(), d_tmp, x.n, to_mont, 1, st);
+    BH_TRY_HIP(hipGetLastError());
+    BH_TRY_HIP(hipMemcpyAsync(x.host, d_tmp, x.n * 32, hipMemcpyDeviceToHost, st));
+    BH_TRY_HIP(hipStreamSynchronize(st));
+  }
+  if (a_aux_density) memcpy(a_aux_density, w->a_aux_density.data(), w->a_aux_words * 8);
+  if (b_input_density) memcpy(b_input_density, w->b_input_density.data(), w->b_in_words * 8);
+  if (b_aux_density) memcpy(b_aux_density, w->b_aux_density.data(), w->b_aux_words * 8);
   return BH_OK;
 }
 

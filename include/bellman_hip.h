@@ -414,6 +414,32 @@ bh_status bh_generate_parameters(bh_ctx* ctx, const bh_r1cs* r, const uint64_t a
 /* The MiMC chain's KeypairAssembly (what bh_chain_params synthesizes internally) as a bh_r1cs. */
 bh_status bh_chain_r1cs(bh_ctx* ctx, size_t rounds, uint64_t seed, bh_r1cs** out);
 
+/* ProvingAssignment (prover.rs:55-156, 187-204) evaluated on the device. r holds the circuit;
+ * input_assignment: num_inputs Montgomery Fr (entry 0 is ONE), aux_assignment: num_aux Montgomery Fr.
+ * a = A z, b = B z, c = C z over z = [inputs, aux], including the appended rows input_i * 0 = 0
+ * (a = input_i, b = c = 0); a_aux / b_input / b_aux density bit i = variable i has at least one term
+ * in that matrix, whatever its coefficient (eval calls inc before it looks at the coefficient).
+ * first_unsatisfied (may be null): the least constraint index i with a_i * b_i != c_i, or SIZE_MAX.
+ * The witness is returned either way; the reference's prover does not check satisfaction, this is
+ * TestConstraintSystem::which_is_unsatisfied as one device pass.
+ * The first call on a handle builds the row view of its matrices on the device (8 bytes per term
+ * and 4 per row and row segment, kept with the handle); calls on one handle
+ * run one at a time.  The result is an ordinary bh_witness, freed with bh_witness_free.
+ * BH_ERR_INVALID_ARGUMENT: a null handle or pointer, r on another device than ctx, an assignment
+ * word >= r. */
+bh_status bh_r1cs_witness(bh_ctx* ctx, const bh_r1cs* r, const uint64_t* input_assignment,
+                          const uint64_t* aux_assignment, size_t* first_unsatisfied, bh_witness** out);
+
+/* What a resident witness holds, for tests and callers that want a/b/c back: a, b, c receive m
+ * Montgomery Fr each (m = domain size; entries past num_constraints are the zero padding), inputs /
+ * aux Montgomery, densities as bit words. Any pointer may be null. sizes = {num_constraints, m,
+ * num_inputs, num_aux}.  Works on every witness: uploaded, chain-built or R1CS-built
+ * (prover.rs:206-231 is where the reference holds the same vectors). */
+bh_status bh_witness_sizes(const bh_witness* w, size_t sizes[4]);
+bh_status bh_witness_read(const bh_witness* w, uint64_t* a, uint64_t* b, uint64_t* c, uint64_t* inputs,
+                          uint64_t* aux, uint64_t* a_aux_density, uint64_t* b_input_density,
+                          uint64_t* b_aux_density);
+
 /* ---- per-element variable-base scalar multiplication: the primitive of a ceremony round
  * (make_new_tau_paramter, groth16/mpc.rs:677-706).  Scalars are canonical Fr (4 LE u64 each);
  * the result is a new bh_srs of the input's group and length (bh_srs_free it).
