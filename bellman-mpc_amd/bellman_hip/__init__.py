@@ -179,6 +179,13 @@ def _load():
         "bh_srs_mul_each_bounded": (I, [P, P, P, S, I, P]),
         "bh_srs_mul_powers": (I, [P, P, P, P, I, P]),
         "bh_srs_sub_range": (I, [P, P, S, S, S, P]),
+        "bh_srs_fft": (I, [P, P, I, P]),
+        "bh_srs_read": (I, [P, S, S, P]),
+        "bh_mpc_common_matrix": (I, [P, P, P, P]),
+        "bh_mpc_matrix_vector": (I, [P, I, P]),
+        "bh_mpc_matrix_free": (I, [P]),
+        "bh_mpc_parameters": (I, [P, P, P, P, P]),
+        "bh_mpc_last_matrix_ms": (None, [P]),
         "bh_mpc_common_initial": (I, [P, S, P]),
         "bh_mpc_common_contribute": (I, [P, P, P, P, P, P]),
         "bh_mpc_common_verify": (I, [P, P, P, P, P, P]),
@@ -235,6 +242,8 @@ EXPORTED_SYMBOLS = [
     "bh_mpc_common_len", "bh_mpc_uncommon_initial", "bh_mpc_uncommon_contribute", "bh_mpc_uncommon_verify",
     "bh_mpc_last_miller_ms", "bh_mpc_last_miller_device", "bh_miller_product", "bh_final_exponentiation",
     "bh_verify_batch_device", "bh_proofs_decode", "bh_r1cs_witness", "bh_witness_sizes", "bh_witness_read",
+    "bh_srs_fft", "bh_srs_read", "bh_mpc_common_matrix", "bh_mpc_matrix_vector", "bh_mpc_matrix_free",
+    "bh_mpc_parameters", "bh_mpc_last_matrix_ms",
 ] + [f"bh_mpc_{kind}{who}_{op}" for kind in ("common", "uncommon") for who in ("", "_contrib")
      for op in ("free", "vector", "point", "write", "read")]
 BH_VEC_H, BH_VEC_L, BH_VEC_A, BH_VEC_B_G1, BH_VEC_B_G2 = range(5)
@@ -442,6 +451,23 @@ class Bases:
         h = ctypes.c_void_p()
         _check(_lib.bh_srs_sub_range(self.ctx.h, self.h, lo1, lo2, n, ctypes.byref(h)), "bh_srs_sub_range")
         return Bases._adopt(self.ctx, self.group, h)
+
+    def fft(self, inverse=False):
+        """EvaluationDomain<Point<G>>::fft (domain.rs:81-99) of the vector, natural order; its length
+        must be a power of two from 2 to 2^28."""
+        h = ctypes.c_void_p()
+        _check(_lib.bh_srs_fft(self.ctx.h, self.h, int(bool(inverse)), ctypes.byref(h)), "bh_srs_fft")
+        return Bases._adopt(self.ctx, self.group, h)
+
+    def ifft(self):
+        """The inverse transform (omega^-1, then 1/n): of tau^i G, the Lagrange basis L_i(tau) G."""
+        return self.fft(inverse=True)
+
+    def read(self, first, n):
+        """Bases first .. first + n as uncompressed bytes, in one copy."""
+        out = np.zeros(max(n, 1) * (96 if self.group == BH_G1 else 192), dtype=np.uint8)
+        _check(_lib.bh_srs_read(self.h, first, n, _ptr(out)), "bh_srs_read")
+        return out[:n * (96 if self.group == BH_G1 else 192)].tobytes()
 
     def to_bytes(self):
         return b"".join(self.get(i) for i in range(len(self)))
@@ -1594,6 +1620,7 @@ class Comm:
 (BH_MPC_TAU_G1, BH_MPC_TAU_G2, BH_MPC_ALPHA_TAU_G1, BH_MPC_ALPHA_TAU_G2, BH_MPC_BETA_TAU_G1,
  BH_MPC_BETA_TAU_G2) = range(6)
 BH_MPC_KIN_G1, BH_MPC_KIN_G2, BH_MPC_KOUT_G1, BH_MPC_KOUT_G2, BH_MPC_H_G1, BH_MPC_H_G2 = range(6)
+BH_MPC_MATRIX_A, BH_MPC_MATRIX_B_G1, BH_MPC_MATRIX_B_G2 = 6, 7, 8
 
 
 class _MpcHandle:
@@ -1681,6 +1708,40 @@ class CommonParamterInStorage(_MpcStorage):
                "bh_mpc_common_h_basis")
         return Bases._adopt(self.ctx, BH_G1, a), Bases._adopt(self.ctx, BH_G2, b)
 
+    def matrix(self, r1cs):
+        """CommonParamterInStorage::matrix (mpc.rs:597-645) for any circuit: the Lagrange bases from
+        inverse group FFTs of the storage's vectors, and r1cs's matrices applied to them."""
+        h = ctypes.c_void_p()
+        _check(_lib.bh_mpc_common_matrix(self.ctx.h, self.h, r1cs.h, ctypes.byref(h)), "bh_mpc_common_matrix")
+        return CommonParamterMatrix(self.ctx, h)
+
+
+class CommonParamterMatrix:
+    """mpc.rs:597-645 for one circuit, device-resident: kin and kout (beta A_j + alpha B_j + C_j of the
+    inputs / the aux variables) and h in G1 and G2, and the a, b_g1, b_g2 queries of the Parameters."""
+    _VECTORS = ("kin_g1", "kin_g2", "kout_g1", "kout_g2", "h_g1", "h_g2", "a", "b_g1", "b_g2")
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    def vector(self, which):
+        if isinstance(which, str):
+            which = self._VECTORS.index(which)
+        h = ctypes.c_void_p()
+        _check(_lib.bh_mpc_matrix_vector(self.h, which, ctypes.byref(h)), "bh_mpc_matrix_vector")
+        return BorrowedBases(self.ctx, BH_G2 if which in (1, 3, 5, 8) else BH_G1, h, self)
+
+    def __getattr__(self, name):
+        if name in CommonParamterMatrix._VECTORS:
+            return self.vector(name)
+        raise AttributeError(name)
+
+    def __del__(self):
+        try:
+            _lib.bh_mpc_matrix_free(self.h)
+        except Exception:
+            pass
+
 
 class CommonParamter(_MpcContrib):
     """mpc.rs:362-373: one player's round-one contribution."""
@@ -1740,8 +1801,11 @@ def verify_common_paramter(ctx, storage, new_paramter, z=None):
     return CommonParamterInStorage(ctx, h) if valid.value else None
 
 
-def initial_uncommon_paramters(ctx, front_g1, front_g2, back_g1, back_g2, h_g1, h_g2):
-    """mpc.rs:993-1015 from CommonParamterMatrix's six vectors (Bases)."""
+def initial_uncommon_paramters(ctx, front_g1, front_g2=None, back_g1=None, back_g2=None, h_g1=None, h_g2=None):
+    """mpc.rs:993-1015 from a CommonParamterMatrix (the reference's signature), or from its six
+    vectors (Bases)."""
+    if isinstance(front_g1, CommonParamterMatrix):
+        front_g1, front_g2, back_g1, back_g2, h_g1, h_g2 = (front_g1.vector(k) for k in range(6))
     h = ctypes.c_void_p()
     _check(_lib.bh_mpc_uncommon_initial(ctx.h, front_g1.h, front_g2.h, back_g1.h, back_g2.h, h_g1.h, h_g2.h,
                                         ctypes.byref(h)), "bh_mpc_uncommon_initial")
@@ -1765,3 +1829,12 @@ def verify_uncommon_paramter(ctx, matrix, storage, new_paramter, z=None):
     _check(_lib.bh_mpc_uncommon_verify(ctx.h, matrix.h, storage.h, new_paramter.h, _ptr(_z_words(z)), len(z),
                                        ctypes.byref(valid), ctypes.byref(h)), "bh_mpc_uncommon_verify")
     return UnCommonParamterInStorage(ctx, h) if valid.value else None
+
+
+def generate_parameters_mpc(ctx, round1, matrix, round2):
+    """generate_parameters_mpc (generator.rs:163-237) with the queries filled in: the Parameters of a
+    finished ceremony from its last round-one storage, that storage's matrix and the last round-two
+    storage."""
+    h = ctypes.c_void_p()
+    _check(_lib.bh_mpc_parameters(ctx.h, round1.h, matrix.h, round2.h, ctypes.byref(h)), "bh_mpc_parameters")
+    return Parameters(ctx, h)

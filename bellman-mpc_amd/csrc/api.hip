@@ -920,6 +920,25 @@ bh_status bh_srs_get(const bh_srs* srs, size_t i, uint8_t* out) {
   });
 }
 
+bh_status bh_srs_read(const bh_srs* srs, size_t first, size_t n, uint8_t* out) {
+  if (!srs || (n && !out) || first > srs->n || n > srs->n - first) return BH_ERR_INVALID_ARGUMENT;
+  if (!n) return BH_OK;
+  return with_group(srs->group, [&](auto g) -> bh_status {
+    using G = decltype(g);
+    std::vector<uint32_t> w(n * G::WORDS);
+    BH_TRY_HIP(hipMemcpy(w.data(), srs->pts.as<uint32_t>() + first * G::WORDS, w.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<bool> inf(n, false);
+    for (size_t i : srs->identity_idx)
+      if (i >= first && i - first < n) inf[i - first] = true;
+    for (size_t i = 0; i < n; i++) {
+      typename G::Affine a = G::from_dev_words(&w[i * G::WORDS]);
+      a.infinity = inf[i];
+      to_uncompressed(a, out + i * G::WIRE);
+    }
+    return BH_OK;
+  });
+}
+
 // ---------------------------------------------------------------- multiexp
 bh_status bh_multiexp(bh_ctx* ctx, const bh_srs* bases, size_t base_offset, const uint64_t* density_words,
                       size_t density_len, const uint64_t* exponents, size_t n, int scalar_format, uint8_t* out) {

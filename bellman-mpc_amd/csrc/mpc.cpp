@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <memory>
 
+#include "group_fft.h"
 #include "pairing.h"
 #include "pairing_dev.h"
 #include "r1cs.h"
@@ -54,6 +55,12 @@ struct bh_mpc_common : MpcStorage {};
 struct bh_mpc_uncommon : MpcStorage {};
 struct bh_mpc_common_contrib : MpcContrib {};
 struct bh_mpc_uncommon_contrib : MpcContrib {};
+// CommonParamterMatrix (mpc.rs:597-645) of one circuit: BH_MPC_KIN_G1 .. BH_MPC_MATRIX_B_G2
+struct bh_mpc_matrix {
+  bh_ctx* ctx = nullptr;
+  size_t m = 0, ni = 0, na = 0;
+  std::unique_ptr<bh_srs> v[9];
+};
 
 namespace {
 
@@ -454,6 +461,11 @@ struct CtxLock {
 
 thread_local double g_miller_ms = 0;
 thread_local int g_miller_device = 0;
+thread_local double g_matrix_ms[3] = {0, 0, 0};
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 }  // namespace
 
@@ -733,8 +745,106 @@ bh_status bh_mpc_uncommon_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t
   return contrib_read(ctx, bytes, len, checked, false, out);
 }
 
+// ================================================================ between the rounds
+// CommonParamterInStorage::matrix (mpc.rs:597-645) for any circuit: the Lagrange basis from the
+// inverse transforms of the six vectors' first m elements, the circuit's matrices applied to it
+// (group_fft.hip), and matrixed_h.  The transforms leave the 1/m to the product's coefficients.
+bh_status bh_mpc_common_matrix(bh_ctx* ctx, const bh_mpc_common* st, const bh_r1cs* r, bh_mpc_matrix** out) {
+  if (!ctx || !st || !r || !out || st->ctx->device != ctx->device || r->device != ctx->device)
+    return BH_ERR_INVALID_ARGUMENT;
+  const size_t m = r->m;
+  if (m < 2 || st->v[0]->n / 2 < m) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  std::vector<AffinePt<Fp>> first;
+  bh_status s = download_points<G1Host>(*st->v[0], 1, &first);
+  if (s) return s;
+  uint8_t got[G1Host::WIRE], want[G1Host::WIRE];
+  to_uncompressed(first[0], got);
+  to_uncompressed(g1_gen(), want);
+  if (first[0].infinity || memcmp(got, want, sizeof got)) return BH_ERR_INVALID_ARGUMENT;  // mpc.rs:632
+  std::unique_ptr<bh_mpc_matrix> mx(new bh_mpc_matrix());
+  mx->ctx = ctx;
+  mx->m = m;
+  mx->ni = r->ni;
+  mx->na = r->na;
+  for (auto& v : mx->v) v.reset(new bh_srs());
+  bh_srs lag[6];
+  const bh_srs* lagp[6];
+  for (double& x : g_matrix_ms) x = 0;
+  auto t0 = std::chrono::steady_clock::now();
+  for (int k = 0; k < 6; k++) {
+    if ((s = group_fft(ctx, st->v[k].get(), m, 1, false, &lag[k]))) return s;
+    lagp[k] = &lag[k];
+  }
+  bh_srs* prod[7] = {mx->v[BH_MPC_KIN_G1].get(),  mx->v[BH_MPC_KIN_G2].get(),   mx->v[BH_MPC_KOUT_G1].get(),
+                     mx->v[BH_MPC_KOUT_G2].get(), mx->v[BH_MPC_MATRIX_A].get(), mx->v[BH_MPC_MATRIX_B_G1].get(),
+                     mx->v[BH_MPC_MATRIX_B_G2].get()};
+  g_matrix_ms[0] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  if ((s = matrix_product(ctx, r, lagp, prod))) return s;
+  g_matrix_ms[1] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  if ((s = varbase_sub(ctx, st->v[0].get(), 0, m, m, mx->v[BH_MPC_H_G1].get()))) return s;
+  if ((s = varbase_sub(ctx, st->v[1].get(), 0, m, m, mx->v[BH_MPC_H_G2].get()))) return s;
+  g_matrix_ms[2] = ms_since(t0);
+  *out = mx.release();
+  return BH_OK;
+}
+
+bh_status bh_mpc_matrix_vector(const bh_mpc_matrix* mx, int which, const bh_srs** out) {
+  if (!mx || !out || which < 0 || which > 8) return BH_ERR_INVALID_ARGUMENT;
+  *out = mx->v[which].get();
+  return BH_OK;
+}
+bh_status bh_mpc_matrix_free(bh_mpc_matrix* mx) {
+  delete mx;
+  return BH_OK;
+}
+
+// generate_parameters_mpc (generator.rs:207-236) with the queries filled in
+bh_status bh_mpc_parameters(bh_ctx* ctx, const bh_mpc_common* round1, const bh_mpc_matrix* mx,
+                            const bh_mpc_uncommon* round2, bh_params** out) {
+  if (!ctx || !round1 || !mx || !round2 || !out) return BH_ERR_INVALID_ARGUMENT;
+  if (round1->ctx->device != ctx->device || mx->ctx->device != ctx->device || round2->ctx->device != ctx->device)
+    return BH_ERR_INVALID_ARGUMENT;
+  const size_t want[3] = {mx->ni, mx->na, mx->m};
+  for (int j = 0; j < 3; j++)
+    if (round2->v[2 * j]->n != want[j] || round2->v[2 * j + 1]->n != want[j]) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  std::unique_ptr<bh_params> p(new bh_params());
+  p->ctx = ctx;
+  p->alpha_g1 = round1->p1[0];
+  p->beta_g1 = round1->p1[1];
+  p->beta_g2 = round1->p2[1];
+  p->gamma_g2 = round2->p2[0];
+  p->delta_g1 = round2->p1[1];
+  p->delta_g2 = round2->p2[1];
+  bh_status s = download(round2->v[BH_MPC_KIN_G1].get(), &p->ic);
+  if (s) return s;
+  const struct { const bh_srs* src; size_t n; bh_srs* dst; } q[5] = {
+      {round2->v[BH_MPC_H_G1].get(), mx->m - 1, &p->h},
+      {round2->v[BH_MPC_KOUT_G1].get(), mx->na, &p->l},
+      {mx->v[BH_MPC_MATRIX_A].get(), mx->v[BH_MPC_MATRIX_A]->n, &p->a},
+      {mx->v[BH_MPC_MATRIX_B_G1].get(), mx->v[BH_MPC_MATRIX_B_G1]->n, &p->b_g1},
+      {mx->v[BH_MPC_MATRIX_B_G2].get(), mx->v[BH_MPC_MATRIX_B_G2]->n, &p->b_g2}};
+  for (const auto& x : q) {
+    const size_t bytes = x.n * with_group(x.src->group, [](auto g) { return decltype(g)::WORDS * (size_t)4; });
+    x.dst->ctx = ctx;
+    x.dst->group = x.src->group;
+    x.dst->n = x.n;
+    BH_TRY_HIP(x.dst->pts.alloc(std::max<size_t>(bytes, 16)));
+    if (bytes) BH_TRY_HIP(hipMemcpyAsync(x.dst->pts.p, x.src->pts.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  *out = p.release();
+  return BH_OK;
+}
+
 // wall time (ms) of the per-element Miller loops of this thread's last bh_mpc_common_verify, and
 // how many of its vector pairs ran them on the device
+void bh_mpc_last_matrix_ms(double out[3]) {
+  for (int k = 0; k < 3; k++) out[k] = g_matrix_ms[k];
+}
 double bh_mpc_last_miller_ms(void) { return g_miller_ms; }
 int bh_mpc_last_miller_device(void) { return g_miller_device; }
 

@@ -19,6 +19,7 @@
 
 #include "api_internal.h"
 #include "dist_h.h"
+#include "group_fft.h"
 #include "pairing_dev.h"
 #include "proofs_dev.h"
 #include "r1cs.h"
@@ -90,6 +91,7 @@ bh_status scratch_report(bh_ctx* ctx, uint64_t out[10], std::string* worst) {
   dist_kernels(ks);
   r1cs_kernels(ks);
   varbase_kernels(ks);
+  group_fft_kernels(ks);
   pairing_kernels(ks);
   proofs_kernels(ks);
   const uint64_t cus = (uint64_t)std::max(prop.multiProcessorCount, 1);

@@ -24,6 +24,15 @@ void varbase_kernels(std::vector<KernInfo>& v);  // scratch budget (scratch.cpp)
 // BH_ERR_UNEXPECTED_IDENTITY: an identity in `in`, or a scalar that is zero (found on the device
 // before the normalisation, which a zero ZZ would poison).
 bh_status varbase_mul(bh_ctx* ctx, const bh_srs* in, const uint32_t* d_sc, int stride, int nbits, bh_srs* out);
+// One chunk of that multiplication enqueued on st, for callers that go on with the products
+// unnormalised (group_fft.hip): d_xyzz[i] = k_i * d_pts[i], i < k, as XYZZ.  W windows, the top one
+// biased or not as k_varbase_mul_win takes them (255-bit scalars: W = 64, top_biased = 1).  A
+// product that is the identity is stored as the all-zero point and raises *d_flag.  Workspace:
+// d_xyzz 8 k points, d_scr 8 k field elements + 64 B, d_table 8 k packed records.
+template <class C>
+hipError_t varbase_mul_chunk(const uint32_t* d_pts, const uint32_t* d_sc, int stride, size_t k, int W, int top_biased,
+                             void* d_xyzz, void* d_scr, uint32_t* d_table, uint32_t* d_flag, hipStream_t st);
+constexpr size_t VB_WIN_CHUNK = (size_t)1 << 18;  // points per chunk of the windowed multiplication
 // out[i] = in[lo2 + i] - in[lo1 + i], i < n; a difference that is the identity:
 // BH_ERR_UNEXPECTED_IDENTITY
 bh_status varbase_sub(bh_ctx* ctx, const bh_srs* in, size_t lo1, size_t lo2, size_t n, bh_srs* out);

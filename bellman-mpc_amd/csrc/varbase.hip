@@ -190,10 +190,29 @@ struct VbScratch {
   }
 };
 
+}  // namespace
+
+template <class C>
+hipError_t varbase_mul_chunk(const uint32_t* d_pts, const uint32_t* d_sc, int stride, size_t k, int W, int top_biased,
+                             void* d_xyzz, void* d_scr, uint32_t* d_table, uint32_t* d_flag, hipStream_t st) {
+  using P = typename C::P;
+  hipLaunchKernelGGL(k_varbase_multiples<C>, dim3(nb(k, 256)), dim3(256), 0, st, d_pts, k, reinterpret_cast<P*>(d_xyzz));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if ((e = normalize_batch<C>(d_xyzz, 8 * k, d_scr, d_table, st)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_varbase_mul_win<C>, dim3(nb(k, 256)), dim3(256), 0, st, d_table, d_sc, stride, k, W, top_biased,
+                     reinterpret_cast<P*>(d_xyzz), d_flag);
+  return hipGetLastError();
+}
+template hipError_t varbase_mul_chunk<G1Ops>(const uint32_t*, const uint32_t*, int, size_t, int, int, void*, void*,
+                                             uint32_t*, uint32_t*, hipStream_t);
+template hipError_t varbase_mul_chunk<G2Ops>(const uint32_t*, const uint32_t*, int, size_t, int, int, void*, void*,
+                                             uint32_t*, uint32_t*, hipStream_t);
+
+namespace {
+
 // chunks of VB_WIN_CHUNK points; the table (8 affine records per point) and its XYZZ staging live
 // in a workspace of the call
-constexpr size_t VB_WIN_CHUNK = (size_t)1 << 18;
-
 template <class C>
 bh_status mul_win_t(bh_ctx* ctx, const bh_srs* in, const uint32_t* d_sc, int stride, int nbits, bh_srs* out) {
   using P = typename C::P;
@@ -214,13 +233,8 @@ bh_status mul_win_t(bh_ctx* ctx, const bh_srs* in, const uint32_t* d_sc, int str
   BH_TRY_HIP(hipMemsetAsync(flag.p, 0, 4, ctx->stream));
   for (size_t base = 0; base < n; base += chunk) {
     const size_t k = std::min(chunk, n - base);
-    hipLaunchKernelGGL(k_varbase_multiples<C>, dim3(nb(k, 256)), dim3(256), 0, ctx->stream,
-                       in->pts.as<uint32_t>() + base * words, k, reinterpret_cast<P*>(xyzz.p));
-    BH_TRY_HIP(hipGetLastError());
-    BH_TRY_HIP(normalize_batch<C>(xyzz.p, 8 * k, scr.p, table.as<uint32_t>(), ctx->stream));
-    hipLaunchKernelGGL(k_varbase_mul_win<C>, dim3(nb(k, 256)), dim3(256), 0, ctx->stream, table.as<uint32_t>(),
-                       d_sc + base * (size_t)stride, stride, k, W, top_biased, reinterpret_cast<P*>(xyzz.p),
-                       flag.as<uint32_t>());
+    BH_TRY_HIP(varbase_mul_chunk<C>(in->pts.as<uint32_t>() + base * words, d_sc + base * (size_t)stride, stride, k, W,
+                                    top_biased, xyzz.p, scr.p, table.as<uint32_t>(), flag.as<uint32_t>(), ctx->stream));
     if (bh_status s = finish_chunk<C>(ctx, k, xyzz.p, scr.p, flag.as<uint32_t>(), out->pts.as<uint32_t>() + base * words))
       return s;
   }

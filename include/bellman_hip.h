@@ -25,6 +25,9 @@
  *                          make_new_tau_paramter, matrixed_h groth16/mpc.rs:677-706, 631-635
  *   bh_mpc_common_*        the "common" ceremony round    groth16/mpc.rs:362-414, 708-862
  *   bh_mpc_uncommon_*      the "uncommon" ceremony round  groth16/mpc.rs:891-1131
+ *   bh_srs_fft             EvaluationDomain<Point<G>>::fft / ifft   domain.rs:81-99, 192-228
+ *   bh_mpc_common_matrix   CommonParamterInStorage::matrix, for any circuit   groth16/mpc.rs:597-645
+ *   bh_mpc_parameters      generate_parameters_mpc        groth16/generator.rs:163-237
  *
  * Conventions
  *   - Plain pointers and sizes only; the caller owns every host buffer and the
@@ -114,6 +117,8 @@ bh_status bh_srs_free(bh_srs* srs);
 size_t bh_srs_len(const bh_srs* srs);
 /* read back base i as uncompressed bytes (96/192 B) */
 bh_status bh_srs_get(const bh_srs* srs, size_t i, uint8_t* out);
+/* the same for bases first .. first + n in one copy: out receives n * 96 (192) bytes */
+bh_status bh_srs_read(const bh_srs* srs, size_t first, size_t n, uint8_t* out);
 
 /* ---- multiexp::multiexp.  density_words == NULL means FullDensity.  out: uncompressed
  * encoding of the projective result normalised to affine (96 B for G1, 192 B for G2). */
@@ -464,6 +469,19 @@ bh_status bh_srs_mul_powers(bh_ctx* ctx, const bh_srs* in, const uint64_t a[4], 
                             bh_srs** out);
 bh_status bh_srs_sub_range(bh_ctx* ctx, const bh_srs* in, size_t lo1, size_t lo2, size_t n, bh_srs** out);
 
+/* ---- group-valued FFT of a device point vector: EvaluationDomain<Point<G>>::fft / ifft
+ * (domain.rs:81-99 with Group = Point<G>, 192-228), in G1 or G2.  Natural order in and out; omega is
+ * the root the scalar EvaluationDomain of the same size uses (domain.rs:62-66); inverse != 0 uses
+ * omega^-1 and scales by 1/n.  Applied to tau^i G, the inverse transform gives the Lagrange basis
+ * L_i(tau) G without anyone knowing tau.  n = bh_srs_len(in) must be a power of two, 2 <= n <= 2^28:
+ * anything else is BH_ERR_INVALID_ARGUMENT (a bh_srs cannot hold the identity from_coeffs pads with).
+ * The one deliberate deviation: a butterfly output that is the identity, in any stage or in the
+ * result, returns BH_ERR_UNEXPECTED_IDENTITY and no vector, where the reference would carry the
+ * identity along (it is found on the device before the normalisation it would poison; the call
+ * never returns a wrong point).  For the powers of a tau an honest player drew this happens with
+ * probability at most n log n / r. */
+bh_status bh_srs_fft(bh_ctx* ctx, const bh_srs* in, int inverse, bh_srs** out);
+
 /* ---- the MPC ceremony's parameter rounds (groth16/mpc.rs), for any length and any Fr scalar where
  * the reference hard-codes length 8 and u64.  Handles belong to their context's device; toxic
  * waste is canonical Fr (a word >= r: BH_ERR_INVALID_ARGUMENT, zero: BH_ERR_UNEXPECTED_IDENTITY).
@@ -489,7 +507,7 @@ bh_status bh_srs_sub_range(bh_ctx* ctx, const bh_srs* in, size_t lo1, size_t lo2
  *                             beta, alpha_mul_tau, beta_mul_tau and the lengths.
  *   bh_mpc_common_h_basis     the matrixed_h part of matrix (mpc.rs:631-635): tau[n + i] - tau[i],
  *                             i < n, in both groups; 2n > len: BH_ERR_INVALID_ARGUMENT.  The rest of
- *                             matrix (list_mul_matrix) is the caller's.
+ *                             matrix is bh_mpc_common_matrix, further down.
  *   bh_mpc_common_vector / _point, bh_mpc_common_contrib_vector / _point: borrowed views (valid while
  *                             the handle lives; never bh_srs_free them) and uncompressed bytes
  *   bh_mpc_common_write / _read, bh_mpc_common_contrib_write / _read: the reference keeps these structs
@@ -573,6 +591,49 @@ bh_status bh_mpc_uncommon_contrib_write(const bh_mpc_uncommon_contrib* contrib, 
                                         size_t* written);
 bh_status bh_mpc_uncommon_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
                                        bh_mpc_uncommon_contrib** out);
+/* ---- between the rounds: CommonParamterInStorage::matrix (mpc.rs:597-645) for ANY circuit, and
+ * the Parameters of the finished ceremony (generate_parameters_mpc, generator.rs:163-237, whose a,
+ * b_g1 and b_g2 the reference leaves empty).
+ *   bh_mpc_common_matrix   with m the domain size of r (constraints plus the appended input rows):
+ *                          the inverse bh_srs_fft of the first m elements of the storage's six
+ *                          vectors, then the circuit's matrices applied to those Lagrange bases as
+ *                          list_mul_matrix (mpc.rs:416-457) and eval (generator.rs:411-510) apply
+ *                          them to scalars: out_j = sum over column j's terms of coeff * Lag[row].
+ *                          The handle holds nine vectors (bh_mpc_matrix_vector, borrowed):
+ *                            BH_MPC_KIN_G1 .. BH_MPC_H_G2   kin = beta A_j + alpha B_j + C_j of the
+ *                              inputs, kout the same of the aux variables, each in G1 and G2, and
+ *                              h = bh_mpc_common_h_basis(m): the six of bh_mpc_uncommon_initial
+ *                            BH_MPC_MATRIX_A / _B_G1 / _B_G2   A_j(tau) G1, B_j(tau) G1, B_j(tau) G2
+ *                              over [inputs, aux], identities filtered out with the order kept
+ *                              (generator.rs:614-632)
+ *                          kin is the INPUTS' block: the contract is generate_parameters
+ *                          (generator.rs:520-572), where ic is the inputs' block over gamma and l the
+ *                          aux block over delta.  The reference's matrix puts the aux block in front
+ *                          and initial_uncommon_paramters makes the front kin (mpc.rs:597-612,
+ *                          1008-1011); divided by gamma that is not a Groth16 ic.
+ *                          BH_ERR_INVALID_ARGUMENT: a null handle, a handle of another device,
+ *                          bh_mpc_common_len(storage) < 2m, m < 2, tau_g1[0] not the generator (the
+ *                          reference asserts it, mpc.rs:632).  BH_ERR_UNCONSTRAINED_VARIABLE: an aux
+ *                          variable whose kout is the identity (generator.rs:586-590).
+ *                          BH_ERR_UNEXPECTED_IDENTITY: an identity among kin or h, or from a transform.
+ *   bh_mpc_parameters      generator.rs:207-236 with the queries filled in: vk = alpha_g1, beta_g1,
+ *                          beta_g2 of round one, gamma_g2, delta_g1, delta_g2 of round two, ic = round
+ *                          two's kin_g1; l = kout_g1; h = the first m - 1 of h_g1; a, b_g1, b_g2 from
+ *                          the matrix.  Round-two vectors whose lengths are not the matrix' (inputs,
+ *                          aux, m): BH_ERR_INVALID_ARGUMENT.  The result is an ordinary bh_params. */
+typedef struct bh_mpc_matrix bh_mpc_matrix;
+#define BH_MPC_MATRIX_A 6
+#define BH_MPC_MATRIX_B_G1 7
+#define BH_MPC_MATRIX_B_G2 8
+bh_status bh_mpc_common_matrix(bh_ctx* ctx, const bh_mpc_common* storage, const bh_r1cs* r, bh_mpc_matrix** out);
+bh_status bh_mpc_matrix_vector(const bh_mpc_matrix* matrix, int which, const bh_srs** out);
+bh_status bh_mpc_matrix_free(bh_mpc_matrix* matrix);
+bh_status bh_mpc_parameters(bh_ctx* ctx, const bh_mpc_common* round1, const bh_mpc_matrix* matrix,
+                            const bh_mpc_uncommon* round2, bh_params** out);
+/* wall time (ms) of the parts of this thread's last bh_mpc_common_matrix: [0] the six inverse
+ * transforms, [1] the matrix product, [2] the h basis (every part synchronises) */
+void bh_mpc_last_matrix_ms(double out[3]);
+
 /* wall time (ms) the per-element Miller loops took in this thread's last bh_mpc_common_verify, on
  * whichever path ran them: the device product below (the default), or the host's pool threads
  * (with BH_MPC_HOST_MILLER=1 in the environment, a diagnostic mode, and for a vector pair whose
