@@ -202,6 +202,11 @@ namespace bh {
 bh_status selftest_group_law_kara(int device, int op, const uint32_t* in, size_t n, uint32_t* out,
                                   uint32_t* unit_info);
 }
+// selftest_ntt.hip (tests/test_gpu_ntt_butterfly.py): one butterfly, reduction or store-path
+// transformation of ntt_butterfly.cuh on caller-chosen raw 9-limb operands; kind 0..3: radix-2
+// DIF / DIF unit / DIT / DIT unit, 4..7: radix-4 likewise, 8: fr_qreduce, 9: lw_norm, 10: plain
+// store, 11: SCALARS epilogue (8 packed words out), 12: PRODUCT epilogue
+extern "C" bh_status bh_selftest_ntt_butterfly(int device, int kind, const uint32_t* in, size_t n, uint32_t* out);
 // selftest.hip (tests/test_gpu_accumulate.py): one launch of an accumulation kernel on a
 // caller-ordered, host-validated entry list (group 0: G1, 1: G2; kernel 0: k_accumulate_pf,
 // 1: k_accumulate_g2d; msm_selftest_accumulate in msm_impl.cuh)

@@ -16,6 +16,7 @@
 // that stores the data, indexed by the element's natural index.
 #include "ntt.h"
 #include "ntt_common.cuh"
+#include "ntt_butterfly.cuh"
 #include "msm.h"  // scalars_prepare (one-element epilogue)
 
 namespace bh {
@@ -33,76 +34,6 @@ struct PassArgs {
   int post_lo_bits;
   NttEpilogue epi;          // what the storing pass writes
 };
-
-// ---- limb-wise (carry-free) butterfly arithmetic.  A value handed to fe_mul needs neither
-// normalised limbs nor a reduced value: with limbs < 2^31.4 against a twiddle's normalised limbs
-// a column holds 9 products < 2^60.4 plus 8 m*p products < 2^58 (< 2^63.8 with the carry), and
-// an operand < 12r keeps the product < 2r (12 r^2 < 2^261 r).  So the sums and differences that
-// only feed a product skip the carry chain (1-2 VALU per limb instead of 3-4).
-// K*r with every limb below the top >= J*(2^29-1), i.e. >= a sum of J normalised limbs: J*2^29
-// added to limb i is J taken from limb i+1 (the value is unchanged)
-template <uint32_t K, uint32_t J>
-struct FrBias {
-  struct L { uint32_t v[9]; };
-  static constexpr L make() {
-    L l{};
-    for (int i = 0; i < 9; i++) {
-      int64_t c = KP<FrCfg, K>::value.v[i];
-      if (i < 8) c += (int64_t)J << 29;
-      if (i > 0) c -= J;
-      l.v[i] = (uint32_t)c;
-    }
-    return l;
-  }
-  static constexpr L value = make();
-};
-__device__ __forceinline__ DFr lw_add(const DFr& a, const DFr& b) {
-  DFr r;
-#pragma unroll
-  for (int l = 0; l < 9; l++) r.v[l] = a.v[l] + b.v[l];
-  return r;
-}
-// a + K*r - b limb-wise; b's limbs must be sums of at most J normalised limbs (and its top limb
-// at most K*r's minus J: b < (K/2) r for the callers' bounds)
-template <uint32_t K, uint32_t J>
-__device__ __forceinline__ DFr lw_sub(const DFr& a, const DFr& b) {
-  DFr r;
-#pragma unroll
-  for (int l = 0; l < 9; l++) r.v[l] = a.v[l] + (FrBias<K, J>::value.v[l] - b.v[l]);
-  return r;
-}
-// carry propagation: the same value in normalised limbs (input limbs < 2^31)
-__device__ __forceinline__ DFr lw_norm(const DFr& a) {
-  DFr r;
-  uint32_t c = 0;
-#pragma unroll
-  for (int l = 0; l < 9; l++) {
-    const uint32_t s = a.v[l] + c;
-    r.v[l] = l < 8 ? (s & FrCfg::MASK) : s;
-    c = s >> FrCfg::BITS;
-  }
-  return r;
-}
-
-// x < 2^261 with normalised limbs below the top one -> x - q*r < 2r, one pass instead of a chain
-// of conditional subtractions (fe_csub 16, 8, 4, 2: ~40 VALU each).  r = r8 * 2^232 + r_low with
-// 0 < r_low < 2^232 and x < (x8 + 1) * 2^232, so q = floor(x8 / (r8 + 1)) gives q*r <= x and
-// x - q*r < (r8 + 1 + q) * 2^232 < 2r (q < 2^29 / r8 = 70).  The quotient comes from one FP64
-// fma, exact: (x8 + 1/2) / (r8 + 1) is at least 1/(2(r8 + 1)) ~ 6.6e-8 away from an integer,
-// far beyond the product's rounding (< 71 * 2^-52).
-__device__ __forceinline__ DFr fr_qreduce(const DFr& x) {
-  constexpr double inv = 1.0 / (double)(FrCfg::P[8] + 1u);
-  const uint32_t q = (uint32_t)__builtin_fma((double)x.v[8], inv, 0.5 * inv);
-  DFr r;
-  int64_t c = 0;
-#pragma unroll
-  for (int l = 0; l < 9; l++) {
-    const int64_t t = (int64_t)x.v[l] + c - (int64_t)((uint64_t)q * FrCfg::P[l]);
-    r.v[l] = l < 8 ? ((uint32_t)t & FrCfg::MASK) : (uint32_t)t;
-    c = t >> FrCfg::BITS;  // arithmetic
-  }
-  return r;
-}
 
 // global element index of (group g, position k) for a DIF pass at stages t..t+D-1
 __device__ __forceinline__ uint32_t dif_index(const PassArgs& a, uint32_t g, uint32_t k) {
@@ -168,20 +99,9 @@ __global__ void __launch_bounds__(NTT_T) k_ntt_pass(uint32_t* data, PassArgs a) 
 #pragma unroll
       for (int l = 0; l < 9; l++) { x.v[l] = lds[l * NTT_E + s0]; y.v[l] = lds[l * NTT_E + s1]; }
       DFr nx, ny;
-      if (v == 0) {  // omega_2^0 = 1
-        nx = fe_csub<FrCfg, 2>(fe_add<FrCfg>(x, y));
-        ny = fe_csub<FrCfg, 2>(fe_sub<FrCfg, 2>(x, y));
-      } else {
-        const DFr w = twiddle(v, k & ((1u << hb) - 1), g0 + gl);
-        if (DIF) {
-          nx = fe_csub<FrCfg, 2>(fe_add<FrCfg>(x, y));
-          ny = fe_mul<FrCfg>(lw_sub<4, 1>(x, y), w);
-        } else {  // lazy: no conditional subtraction inside a DIT pass (see the store)
-          const DFr t = fe_mul<FrCfg>(y, w);
-          nx = fe_add<FrCfg>(x, t);
-          ny = fe_sub<FrCfg, 2>(x, t);
-        }
-      }
+      auto w = [&] { return twiddle(v, k & ((1u << hb) - 1), g0 + gl); };  // not read at v == 0 (omega_2^0 = 1)
+      if (DIF) ntt_dif2(x, y, w, v == 0, nx, ny);
+      else ntt_dit2(x, y, w, v == 0, nx, ny);  // lazy: see the store
 #pragma unroll
       for (int l = 0; l < 9; l++) { lds[l * NTT_E + s0] = nx.v[l]; lds[l * NTT_E + s1] = ny.v[l]; }
     }
@@ -211,51 +131,18 @@ __global__ void __launch_bounds__(NTT_T) k_ntt_pass(uint32_t* data, PassArgs a) 
         const int v = a.L - u - 1, v2 = v - 1;
         const uint32_t m1 = (1u << hb) - 1, m2 = (1u << (hb - 1)) - 1;
         const DFr wa0 = twiddle(v, ks[0] & m1, g), wa1 = twiddle(v, ks[1] & m1, g);
-        // inputs < 2r (normalised); the sums feeding y0/y1 and the differences feeding the
-        // products stay limb-wise (see lw_sub), y0/y2 are carried and reduced back below 2r
-        const DFr s02 = lw_add(x[0], x[2]), s13 = lw_add(x[1], x[3]);  // < 4r, limbs < 2^30
-        const DFr u2 = fe_mul<FrCfg>(lw_sub<4, 1>(x[0], x[2]), wa0);   // < 2r
-        const DFr u3 = fe_mul<FrCfg>(lw_sub<4, 1>(x[1], x[3]), wa1);
-        y[0] = fr_qreduce(fe_add<FrCfg>(s02, s13));                  // < 8r
-        y[2] = fe_csub<FrCfg, 2>(fe_add<FrCfg>(u2, u3));                // < 4r
-        if (v2 == 0) {  // omega_2^0 = 1
-          y[1] = fr_qreduce(lw_norm(lw_sub<8, 2>(s02, s13)));           // < 12r
-          y[3] = fr_qreduce(lw_norm(lw_sub<4, 1>(u2, u3)));             // < 6r
-        } else {
-          const DFr wb = twiddle(v2, ks[0] & m2, g);
-          y[1] = fe_mul<FrCfg>(lw_sub<8, 2>(s02, s13), wb);  // operand < 12r, limbs < 2^31.4
-          y[3] = fe_mul<FrCfg>(lw_sub<4, 1>(u2, u3), wb);
-        }
+        auto wb = [&] { return twiddle(v2, ks[0] & m2, g); };  // not read at v2 == 0 (omega_2^0 = 1)
+        ntt_dif4(x, wa0, wa1, wb, v2 == 0, y);
       } else {
         // stage u (distance 2^hb): (k0, k1), (k2, k3); stage u+1 (2^(hb+1)): (k0, k2), (k1, k3).
-        // Lazy reduction: a DIT stage adds a product (< 2r) to, or subtracts it (+2r) from, a value
-        // < B, so values stay < 2r(D+1) <= 22r < 2^261 in the 9 limbs, and a Montgomery product
-        // of such a value with a twiddle (< r) still ends < 2r (22 r^2 < 2^261 r); the storing
-        // pass reduces.  v == 0 only occurs at global stage 0, on freshly loaded values (< 2r).
+        // Lazy reduction (ntt_dit4): values grow by 4r per step and the storing pass reduces.
+        // v == 0 only occurs at global stage 0, on freshly loaded values (< 2r).
         const int v = u, v2 = u + 1;
         const uint32_t m1 = (1u << hb) - 1, m2 = (2u << hb) - 1;
-        // u0, u1 stay limb-wise (u1's top limb may wrap: it only reaches carried sums, whose
-        // values are non-negative), u2, u3 are operands of products (limb-wise, < 26r)
-        DFr a0, a1, p2, p3;
-        if (v == 0) {  // omega_2^0 = 1
-          a0 = fe_csub<FrCfg, 2>(fe_add<FrCfg>(x[0], x[1]));
-          a1 = fe_csub<FrCfg, 2>(fe_sub<FrCfg, 2>(x[0], x[1]));
-          p2 = fe_csub<FrCfg, 2>(fe_add<FrCfg>(x[2], x[3]));
-          p3 = fe_csub<FrCfg, 2>(fe_sub<FrCfg, 2>(x[2], x[3]));
-        } else {
-          const DFr wa = twiddle(v, ks[0] & m1, g);
-          const DFr t0 = fe_mul<FrCfg>(x[1], wa), t1 = fe_mul<FrCfg>(x[3], wa);
-          a0 = lw_add(x[0], t0);
-          a1 = lw_sub<2, 1>(x[0], t0);
-          p2 = lw_add(x[2], t1);
-          p3 = lw_sub<4, 1>(x[2], t1);
-        }
-        const DFr wb0 = twiddle(v2, ks[0] & m2, g), wb1 = twiddle(v2, ks[1] & m2, g);
-        const DFr s0 = fe_mul<FrCfg>(p2, wb0), s1 = fe_mul<FrCfg>(p3, wb1);
-        y[0] = fe_add<FrCfg>(a0, s0);
-        y[2] = lw_norm(lw_sub<2, 1>(a0, s0));
-        y[1] = fe_add<FrCfg>(a1, s1);
-        y[3] = lw_norm(lw_sub<2, 1>(a1, s1));
+        auto wa = [&] { return twiddle(v, ks[0] & m1, g); };  // not read at v == 0 (omega_2^0 = 1)
+        auto wb0 = [&] { return twiddle(v2, ks[0] & m2, g); };
+        auto wb1 = [&] { return twiddle(v2, ks[1] & m2, g); };
+        ntt_dit4(x, wa, wb0, wb1, v == 0, y);
       }
 #pragma unroll
       for (int q = 0; q < 4; q++) {
@@ -279,25 +166,20 @@ __global__ void __launch_bounds__(NTT_T) k_ntt_pass(uint32_t* data, PassArgs a) 
     for (int l = 0; l < 9; l++) x.v[l] = lds[l * NTT_E + slot];
     const uint32_t nat = DIF ? brev(idx, a.L) : idx;
     if (a.post_hi) x = fe_mul<FrCfg>(x, pow_factor(a.post_lo, a.post_hi, a.post_lo_bits, nat));  // < 2r
-    if (a.epi.kind == NttEpilogue::PRODUCT) {  // x = b (< 22r, normalised limbs): pa[idx] = pa[idx] * x * k
-      // pa < 2r, so pa * x < 44 r^2 < 2^261 r and the Montgomery product ends < 2r
-      const DFr p = fe_mul<FrCfg>(ld_packed(a.epi.pa, idx), x);
-      st_packed(a.epi.pa, idx, fe_mul<FrCfg>(p, ld_limbs(a.epi.k, 0)));
+    auto sub = [&] { return ld_packed(a.epi.sub, idx); };  // read only where a.epi.sub is set
+    if (a.epi.kind == NttEpilogue::PRODUCT) {  // x = b: pa[idx] = pa[idx] * x * k
+      st_packed(a.epi.pa, idx, ntt_store_product(ld_packed(a.epi.pa, idx), x, ld_limbs(a.epi.k, 0)));
     } else if (a.epi.kind == NttEpilogue::SCALARS) {  // canonical scalar at the natural index
       if (nat < a.epi.n_out) {
-        // x + 2r - sub[idx]: sub < 2r, and x < 2r (post-scaled or a DIF value; < 22r from a bare DIT)
-        if (a.epi.sub) x = fe_sub<FrCfg, 2>(x, ld_packed(a.epi.sub, idx));
         uint32_t w8[8];
-        // x < 24r < 2^261 (< 4r in the H block), so x * 2^-261 <= r: one subtraction
-        fe_pack<FrCfg>(fe_csub<FrCfg, 1>(fe_from_mont<FrCfg>(x)), w8);
+        ntt_store_scalars(x, a.epi.sub != nullptr, sub, w8);
         uint4* q = reinterpret_cast<uint4*>(a.epi.out + (size_t)nat * 8);
         q[0] = make_uint4(w8[0], w8[1], w8[2], w8[3]);
         q[1] = make_uint4(w8[4], w8[5], w8[6], w8[7]);
       }
     } else {
-      if (!DIF && !a.post_hi) x = fr_qreduce(x);  // a lazily reduced DIT value (< 22r) -> < 2r for the packed form
-      // x < 2r and sub < 2r: x + 2r - sub < 4r, one conditional subtraction back below 2r
-      if (a.epi.sub) x = fe_csub<FrCfg, 2>(fe_sub<FrCfg, 2>(x, ld_packed(a.epi.sub, idx)));
+      // a bare DIT value is lazily reduced (< 22r); post-scaled and DIF values are < 2r
+      ntt_store_plain(x, !DIF && !a.post_hi, a.epi.sub != nullptr, sub);
       st_packed(data, idx, x);
     }
   }

@@ -141,3 +141,116 @@ def test_fp2_lazy_karatsuba_product_columns_stay_below_the_fence():
     assert worst_lo >= 0
     assert worst_hi < FENCE and worst_hi < 1 << 64
     assert worst_hi < 611 * (1 << 58) // 10     # "< 61.1 * 2^58" in field.cuh
+
+
+# ---------------------------------------------------------------- the NTT's unnormalised operands
+# csrc/ntt_butterfly.cuh hands fe_mul<FrCfg> limb-wise sums and differences (lw_add, lw_sub<K, J>)
+# whose limbs exceed 29 bits: the largest operands that product ever sees.
+
+def _kp(p, k):
+    """KP<C, K>::make(): K * p in normalised limbs"""
+    out, carry = [], 0
+    for limb in p:
+        t = limb * k + carry
+        out.append(t & MASK)
+        carry = t >> BITS
+    assert carry == 0
+    return out
+
+
+def _fr_bias(k, j):
+    """FrBias<K, J>::make(): K * r with J * 2^29 lent to every limb below the top by the limb above"""
+    n = len(FR)
+    out = []
+    for i, c in enumerate(_kp(FR, k)):
+        if i < n - 1:
+            c += j << BITS
+        if i > 0:
+            c -= j
+        assert 0 <= c < 1 << 32
+        out.append(c)
+    return out
+
+
+def _fr_value(limbs):
+    return sum(v << (BITS * i) for i, v in enumerate(limbs))
+
+
+def _top(v):
+    return v >> (BITS * (len(FR) - 1))
+
+
+def _ntt_operand_maxima():
+    """per-limb maxima of every limb-wise expression the butterflies hand to fe_mul<FrCfg>; a
+    normalised value < K r has limbs 0..7 <= MASK and a top limb <= top(K r - 1)"""
+    r = _fr_value(FR)
+    n = len(FR)
+
+    def norm(k):
+        return [MASK] * (n - 1) + [_top(k * r - 1)]
+
+    def add(a, b):
+        return [x + y for x, y in zip(a, b)]
+
+    def sub(k, j, a, b):
+        bias = _fr_bias(k, j)
+        # no limb of the subtrahend exceeds the bias: limbs below the top are sums of J normalised limbs
+        assert all(bias[i] >= b[i] for i in range(n)), (k, j)
+        return add(a, bias)     # the subtrahend at zero
+    two = norm(2)
+    s = add(two, two)                           # s02, s13: lw_add of two normalised values < 2r
+    return {
+        "dif lw_sub<4,1>(x, y)": sub(4, 1, two, two),
+        "dif lw_sub<8,2>(s02, s13)": sub(8, 2, s, s),
+        "dit a0 / p2 = lw_add(x, t), x < 18r": add(norm(18), two),
+        "dit p3 = lw_sub<4,1>(x, t), x < 18r": sub(4, 1, norm(18), two),
+        "dit a1 = lw_sub<2,1>(x, t), x < 18r": add(norm(18), _fr_bias(2, 1)),    # not a product operand
+    }
+
+
+def test_fr_bias_keeps_the_value_and_covers_its_subtrahend():
+    r = _fr_value(FR)
+    for k, j in ((2, 1), (4, 1), (8, 2)):
+        bias = _fr_bias(k, j)
+        assert _fr_value(bias) == k * r
+        assert all(b >= j * MASK for b in bias[:-1])
+        # the top limb covers a subtrahend < (K / 2) r, except FrBias<2, 1> against a product whose
+        # top limb equals 2r's (ntt_dit4's a1: the wrap the carried sums undo)
+        assert bias[-1] >= _top((k // 2) * r - 1) - (1 if (k, j) == (2, 1) else 0)
+
+
+def test_ntt_operand_columns_stay_below_the_fence():
+    """fe_mul<FrCfg> of each limb-wise operand against a factor with 29-bit limbs (a twiddle, and a
+    superset of it: every limb at 2^29 - 1)"""
+    n = len(FR)
+    twiddle = [MASK] * n
+    worst = {}
+    for name, limbs in _ntt_operand_maxima().items():
+        if "a1" in name:
+            continue
+        assert max(limbs) <= 5 * (1 << BITS) - 3, name
+        worst[name] = _walk_unsigned(FR, lambda k, la=limbs: _colsum(k, la, twiddle), p0_one=True)
+        assert worst[name] < FENCE, (name, worst[name])
+    # the margin is real and under half a bit: every limb at 5 * 2^29 stays inside, at 2^32 - 1 it does not
+    assert max(worst.values()) <= _walk_unsigned(FR, lambda k: _colsum(k, [5 << BITS] * n, twiddle), True) < FENCE
+    assert _walk_unsigned(FR, lambda k: _colsum(k, [(1 << 32) - 1] * n, twiddle), True) > FENCE
+    assert max(worst.values()) < 2 ** 63.4      # the figure quoted in ntt_butterfly.cuh
+
+
+def test_lw_norm_inputs_plus_carry_fit_32_bits():
+    """lw_norm adds the carry to each limb in 32 bits: at its call sites (ntt_dif4's unit branch,
+    ntt_dit4's y2 and y3) no limb plus the carry into it reaches 2^32"""
+    m = _ntt_operand_maxima()
+    bias21 = _fr_bias(2, 1)
+    sites = {
+        "dif y1": m["dif lw_sub<8,2>(s02, s13)"],
+        "dif y3": m["dif lw_sub<4,1>(x, y)"],
+        "dit y2": [a + b for a, b in zip(m["dit a0 / p2 = lw_add(x, t), x < 18r"], bias21)],
+        "dit y3": [a + b for a, b in zip(m["dit a1 = lw_sub<2,1>(x, t), x < 18r"], bias21)],
+    }
+    for name, limbs in sites.items():
+        carry = 0
+        for v in limbs:
+            assert v + carry < 1 << 32, name
+            carry = (v + carry) >> BITS
+        assert max(limbs[:-1]) <= 5 * (1 << BITS) - 3, name

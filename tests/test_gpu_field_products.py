@@ -6,7 +6,11 @@ split column chains and a merge add per column and once with carry-seeded column
 (BH_COLUMN_CHAIN).  Only the association order of exact 64-bit sums differs between the two, so
 their limbs must be identical; the values are checked modulo p or r.  One launch of a few
 workgroups covers zero and one, p - 1, p, 2p - 1, 127p + (p - 1), every limb at 2^29 - 1 where a
-form's bound allows it, a single non-zero limb at each position, and 4 096 random values."""
+form's bound allows it, a single non-zero limb at each position, and 4 096 random values.
+
+The Fr product also takes the NTT's unnormalised operands (csrc/ntt_butterfly.cuh): a normalised
+value plus a bias K r whose limbs carry J 2^29 lent from the limb above, limb-wise, with limbs up to
+5 * 2^29 - 3 and values up to 26r - 1, against a factor below r."""
 import ctypes
 import random
 
@@ -53,7 +57,31 @@ def _cases():
     for _ in range(4096):
         ops = [rng.randrange(128 * P) for _ in range(4)] + [rng.randrange(1 << 386) for _ in range(4)]
         cases.append((ops, [rng.randrange(8 * R) for _ in range(2)]))
+    # Fr: unnormalised left operands (raw limbs) against a factor below r
+    low_full = (1 << (BITS * (NR - 1))) - 1
+    factors = [0, 1, R - 1, RR % R, low_full] + [rng.randrange(R) for _ in range(3)]
+    for k, j in ((2, 1), (4, 1), (8, 2)):
+        bias = _fr_bias(k, j)
+        top = (26 - k) * R - 1                      # the value stays <= 26r - 1
+        vals = [0, 1, R, top, low_full, (top >> (BITS * (NR - 1)) << (BITS * (NR - 1))) - 1]
+        vals += [rng.randrange(top + 1) for _ in range(10)]
+        for v in vals:
+            for m in range(1, j + 1):               # a sum of m <= J normalised values, limb-wise
+                parts = [v - (m - 1) * (v // m)] + [v // m] * (m - 1)
+                x = [sum(t) for t in zip(bias, *(_limbs(q, NR) for q in parts))]
+                assert _value(x) == v + k * R < 26 * R and max(x) <= 5 * (1 << BITS) - 3
+                cases += [([0] * 8, [x, f]) for f in factors]
+    # the largest limbs the butterflies produce: every low limb of both summands at 2^29 - 1, plus FrBias<8, 2>
+    x = [2 * a + b for a, b in zip(_limbs(low_full, NR), _fr_bias(8, 2))]
+    assert 9 << (BITS - 1) < max(x) <= 5 * (1 << BITS) - 3 and _value(x) < 26 * R
+    cases += [([0] * 8, [x, f]) for f in factors]
     return cases
+
+
+def _fr_bias(k, j):
+    """FrBias<K, J> of csrc/ntt_butterfly.cuh: K r, each limb below the top with J 2^29 lent by the limb above"""
+    kr = _limbs(k * R, NR)
+    return [kr[i] + ((j << BITS) if i < NR - 1 else 0) - (j if i > 0 else 0) for i in range(NR)]
 
 
 def _run(cases):
@@ -61,7 +89,8 @@ def _run(cases):
     f = bh.lib().bh_selftest_field_products
     f.restype = ctypes.c_int
     f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    inp = np.array([sum((_limbs(x, NP) for x in fp), []) + sum((_limbs(x, NR) for x in fr), []) for fp, fr in cases],
+    inp = np.array([sum((_limbs(x, NP) for x in fp), []) +
+                    sum((_limbs(x, NR) if isinstance(x, int) else list(x) for x in fr), []) for fp, fr in cases],
                    dtype=np.uint32)
     assert inp.shape == (len(cases), N_IN)
     out = np.zeros((len(cases), 2, N_OUT), dtype=np.uint32)
@@ -77,7 +106,7 @@ def test_every_product_form_matches_integers_and_both_column_forms_agree():
     rpi, rri = pow(RP, -1, P), pow(RR, -1, R)
     for (fp, fr), res in zip(cases, out[:, 1, :]):
         a, b, c, d, e, f, g, h = fp
-        x, y = fr
+        x, y = (v if isinstance(v, int) else _value(v) for v in fr)
         got = [_value(res[k * NP:(k + 1) * NP]) for k in range(8)]
         in_bound = max(a, b, c, d) < 128 * P
         want = [a * b * rpi, a * a * rpi, (a * b + c * d) * rpi, a * rpi]
@@ -95,4 +124,6 @@ def test_every_product_form_matches_integers_and_both_column_forms_agree():
         s = _value(res[8 * NP:])
         assert s % R == x * y * rri % R, fr
         if max(x, y) < 8 * R:
+            assert s < 2 * R, fr
+        if x < 26 * R and y < R:    # the NTT's rule: an operand below 26r times a factor below r (26 r^2 < 2^261 r)
             assert s < 2 * R, fr

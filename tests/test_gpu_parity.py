@@ -323,6 +323,33 @@ def test_fft_full_range_and_extreme_values_equal_oracle(ctx, logm):
             assert d.into_coeffs() == [int(x) for x in o.coeffs], (name, op, logm)
 
 
+_ALL_FFTS = ("fft", "ifft", "coset_fft", "icoset_fft")
+
+
+@pytest.mark.parametrize("logm,ops,names", [(13, _ALL_FFTS, ("random", "r-1")), (15, _ALL_FFTS, ("random", "r-1")),
+                                            (17, ("fft", "ifft"), ("random",))])
+def test_fft_pass_splits_equal_oracle(ctx, logm, ops, names):
+    """The pass splits no other direct transform test visits (launch_ntt: 2^13 = [6, 7], 2^15 =
+    [8, 7], 2^17 = [8, 9]; the odd pass runs a radix-2 stage first), element for element against
+    the oracle's serial_fft, so that a wrong element there names the transform and not a proof."""
+    bh = _bh()
+    from oracle import bellman as bm
+    E = bm.BLS12_381
+    m = 1 << logm
+    rng = np.random.default_rng(100 + logm)
+    cases = {
+        "random": [int.from_bytes(rng.bytes(32), "little") % R for _ in range(m)],
+        "r-1": [R - 1] * m,
+    }
+    for name in names:
+        for op in ops:
+            d = bh.EvaluationDomain(ctx, cases[name])
+            getattr(d, op)()
+            o = bm.EvaluationDomain(E, list(cases[name]))
+            getattr(o, op)()
+            assert d.into_coeffs() == [int(x) for x in o.coeffs], (name, op, logm)
+
+
 def test_compute_h_golden(ctx, golden):
     bh = _bh()
     g = golden["h_random"]

@@ -1,4 +1,4 @@
-"""The arithmetic behind the NTT's one-step reduction (ntt.hip fr_qreduce) and its pass split,
+"""The arithmetic behind the NTT's one-step reduction (ntt_butterfly.cuh fr_qreduce) and its pass split,
 restated on the host: the device kernels themselves are checked against the oracle by the GPU
 parity tests (golden domains, extreme values, every proof); these pin the bounds they rely on.
 
