@@ -242,6 +242,20 @@ extern "C" bh_status bh_selftest_miller_product(bh_ctx* ctx, const bh_srs* g1, s
 // c1; a value >= p: BH_ERR_INVALID_ARGUMENT).  out per value: the is-square flag (1 / 0), then the
 // canonical root the routine left (12 or 24 words; a root of the value when the flag is 1)
 extern "C" bh_status bh_selftest_field_sqrt(int device, int field, const uint32_t* in, size_t n, uint32_t* out);
+// dist_h.hip (tests/test_gpu_dist_h.py): the distributed H pipeline with nranks virtual ranks on one
+// context, every phase through dist_h_phase1/2/3/final and the exchanges as device copies.  a, b, c:
+// m bls12_381-Montgomery Fr each (m a power of two with dist_h_eligible(nranks, log m)).  Every
+// rank's hbuf and hidx as the kernels left them, rank-major: nranks * M canonical scalars (8 words)
+// in h_out, nranks * M indices in idx_out (M = m / nranks)
+extern "C" bh_status bh_selftest_dist_h(bh_ctx* ctx, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t m,
+                                        int nranks, uint32_t* h_out, int32_t* idx_out);
+// one rank's one kernel on caller-chosen packed words (8 per value, each value < 2r), used as given.
+// stage 0 (dist_h_phase2): recv = 3 M values [vec][source rank][C]; out = the 2 M values of a's and
+// b's rows in work, out2 = the M values of cprime.  stage 1 (dist_h_final): recv = M values
+// [source rank][C], cprime = M values; out = hbuf (M x 8 words), out2 = hidx (M int32)
+extern "C" bh_status bh_selftest_dist_stage(bh_ctx* ctx, int log_m, int nranks, int rank, int stage,
+                                            const uint32_t* recv, const uint32_t* cprime, uint32_t* out,
+                                            uint32_t* out2);
 // prover.hip (tests/test_proof_schedule_cpu.py): proof_schedule() of proof_schedule.h on flat arrays
 extern "C" int bh_selftest_proof_schedule(const uint64_t* jobs, const uint8_t* rel, unsigned flags, int64_t* out,
                                           size_t cap);

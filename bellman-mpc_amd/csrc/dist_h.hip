@@ -13,6 +13,14 @@
 //   forward  V[N j + r] = NTT_M over q of  w^(q r) * sum_t w_N^(t r) * v[M t + q]
 // so each transform is a local M-point NTT (existing LDS passes), an all-to-all of C = M/N
 // element chunks and, per q, an N-point DFT with the w^(+-q r) twiddles, done in registers.
+//
+// Operand contract: every packed value k_dist_mid and k_dist_final load (the exchanged chunks and
+// cprime) is below 2r, which the local NTT's stores guarantee; every packed value they store (work's
+// a and b rows, cprime) is below 2r again, and hbuf holds canonical scalars (below r).  The N-point
+// DFT keeps that bound by one conditional subtraction of 2r per butterfly output, and geometric()
+// passes x[0] through as loaded.  bh_selftest_dist_h (the whole pipeline with N virtual ranks on one
+// stream) and bh_selftest_dist_stage (one rank's one kernel on chosen packed words) at the end of
+// this file let tests/test_gpu_dist_h.py hold the kernels to it against tests/dist_h_model.py.
 #include "dist_h.h"
 #include "ntt_common.cuh"
 
@@ -305,4 +313,120 @@ void dist_kernels(std::vector<KernInfo>& v) {
   v.push_back({"k_dist_final<16>", (const void*)k_dist_final<16>, 256, 0});
 }
 
+// ------------------------------------------------------------------ self-tests (api_internal.h)
+namespace {
+
+// LocalExchanger's rule (prover.hip) between the virtual ranks of one stream: chunk r of rank p's
+// send buffer -> chunk p of rank r's receive buffer, for nvec vectors of stride M
+bh_status selftest_exchange(std::vector<DistH>& d, bool work_to_recv, int nvec, hipStream_t st) {
+  const size_t N = d.size(), M = d[0].M, C = d[0].C;
+  for (size_t r = 0; r < N; r++)
+    for (size_t p = 0; p < N; p++)
+      for (int v = 0; v < nvec; v++) {
+        const uint32_t* send = (work_to_recv ? d[p].work : d[p].recv).as<uint32_t>();
+        uint32_t* recv = (work_to_recv ? d[r].recv : d[r].work).as<uint32_t>();
+        BH_TRY_HIP(hipMemcpyAsync(recv + ((size_t)v * M + p * C) * 8, send + ((size_t)v * M + r * C) * 8, C * 32,
+                                  hipMemcpyDeviceToDevice, st));
+      }
+  return BH_OK;
+}
+
+bh_status selftest_pipeline(bh_ctx* ctx, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t m, int N,
+                            int L, uint32_t* h_out, int32_t* idx_out) {
+  hipStream_t st = ctx->stream;
+  DevBuf abc;
+  BH_TRY_HIP(abc.alloc(3 * m * 32));
+  std::vector<DistH> d(N);
+  bh_status s;
+  for (int r = 0; r < N; r++)
+    if ((s = dist_h_init(ctx, d[r], N, r, L))) return s;
+  uint32_t* full = abc.as<uint32_t>();
+  if ((s = upload_fr(ctx, a, m, m, full)) || (s = upload_fr(ctx, b, m, m, full + m * 8)) ||
+      (s = upload_fr(ctx, c, m, m, full + 2 * m * 8)))
+    return s;
+  for (int r = 0; r < N; r++)
+    if ((s = dist_h_phase1(ctx, d[r], full, st))) return s;
+  if ((s = selftest_exchange(d, true, 3, st))) return s;
+  for (int r = 0; r < N; r++)
+    if ((s = dist_h_phase2(ctx, d[r], st))) return s;
+  if ((s = selftest_exchange(d, true, 2, st))) return s;
+  for (int r = 0; r < N; r++)
+    if ((s = dist_h_phase3(ctx, d[r], st))) return s;
+  if ((s = selftest_exchange(d, false, 1, st))) return s;
+  for (int r = 0; r < N; r++)
+    if ((s = dist_h_final(ctx, d[r], st))) return s;
+  const size_t M = d[0].M;
+  for (int r = 0; r < N; r++) {
+    BH_TRY_HIP(hipMemcpyAsync(h_out + (size_t)r * M * 8, d[r].hbuf.p, M * 32, hipMemcpyDeviceToHost, st));
+    BH_TRY_HIP(hipMemcpyAsync(idx_out + (size_t)r * M, d[r].hidx.p, M * 4, hipMemcpyDeviceToHost, st));
+  }
+  BH_TRY_HIP(hipStreamSynchronize(st));
+  return BH_OK;
+}
+
+bh_status selftest_stage(bh_ctx* ctx, int L, int N, int rank, int stage, const uint32_t* recv, const uint32_t* cprime,
+                         uint32_t* out, uint32_t* out2) {
+  hipStream_t st = ctx->stream;
+  DistH d;
+  bh_status s = dist_h_init(ctx, d, N, rank, L);
+  if (s) return s;
+  const size_t M = d.M;
+  // what the kernel is to write starts as all ones: a slot it left alone is not below 2r
+  BH_TRY_HIP(hipMemsetAsync(d.cprime.p, 0xFF, M * 32, st));
+  if (stage == 0) {
+    BH_TRY_HIP(hipMemcpyAsync(d.recv.p, recv, 3 * M * 32, hipMemcpyHostToDevice, st));
+    BH_TRY_HIP(hipMemsetAsync(d.work.p, 0xFF, 3 * M * 32, st));
+    if ((s = dist_h_phase2(ctx, d, st))) return s;
+    BH_TRY_HIP(hipMemcpyAsync(out, d.work.p, 2 * M * 32, hipMemcpyDeviceToHost, st));
+    BH_TRY_HIP(hipMemcpyAsync(out2, d.cprime.p, M * 32, hipMemcpyDeviceToHost, st));
+  } else {
+    BH_TRY_HIP(hipMemcpyAsync(d.work.p, recv, M * 32, hipMemcpyHostToDevice, st));  // where k_dist_final reads
+    BH_TRY_HIP(hipMemcpyAsync(d.cprime.p, cprime, M * 32, hipMemcpyHostToDevice, st));
+    BH_TRY_HIP(hipMemsetAsync(d.hbuf.p, 0xFF, M * 32, st));
+    BH_TRY_HIP(hipMemsetAsync(d.hidx.p, 0xFF, M * 4, st));
+    if ((s = dist_h_final(ctx, d, st))) return s;
+    BH_TRY_HIP(hipMemcpyAsync(out, d.hbuf.p, M * 32, hipMemcpyDeviceToHost, st));
+    BH_TRY_HIP(hipMemcpyAsync(out2, d.hidx.p, M * 4, hipMemcpyDeviceToHost, st));
+  }
+  BH_TRY_HIP(hipStreamSynchronize(st));
+  return BH_OK;
+}
+
+}  // namespace
 }  // namespace bh
+
+extern "C" {
+
+bh_status bh_selftest_dist_h(bh_ctx* ctx, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t m, int nranks,
+                             uint32_t* h_out, int32_t* idx_out) {
+  using namespace bh;
+  if (!ctx || !a || !b || !c || !h_out || !idx_out) return BH_ERR_INVALID_ARGUMENT;
+  if (m == 0 || (m & (m - 1)) || m > ((size_t)1 << 30)) return BH_ERR_INVALID_ARGUMENT;
+  const int L = log2i((int)m);
+  if (!dist_h_eligible(nranks, L)) return BH_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  BH_TRY_HIP(hipSetDevice(ctx->device));
+  bh_status s = scratch_check(ctx);
+  if (s) return s;
+  s = selftest_pipeline(ctx, a, b, c, m, nranks, L, h_out, idx_out);
+  if (s) (void)hipStreamSynchronize(ctx->stream);  // nothing in flight when the ranks' buffers go
+  return s;
+}
+
+bh_status bh_selftest_dist_stage(bh_ctx* ctx, int log_m, int nranks, int rank, int stage, const uint32_t* recv,
+                                 const uint32_t* cprime, uint32_t* out, uint32_t* out2) {
+  using namespace bh;
+  if (!ctx || !recv || !out || !out2 || (stage == 1 && !cprime)) return BH_ERR_INVALID_ARGUMENT;
+  if (stage != 0 && stage != 1) return BH_ERR_INVALID_ARGUMENT;
+  if (log_m < 0 || log_m > 30 || !dist_h_eligible(nranks, log_m) || rank < 0 || rank >= nranks)
+    return BH_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  BH_TRY_HIP(hipSetDevice(ctx->device));
+  bh_status s = scratch_check(ctx);
+  if (s) return s;
+  s = selftest_stage(ctx, log_m, nranks, rank, stage, recv, cprime, out, out2);
+  if (s) (void)hipStreamSynchronize(ctx->stream);
+  return s;
+}
+
+}  // extern "C"
