@@ -198,6 +198,8 @@ def _load():
         "bh_mpc_last_miller_device": (I, []),
         "bh_miller_product": (I, [P, P, S, P, S, S, P]),
         "bh_final_exponentiation": (I, [P, P]),
+        "bh_final_exponentiation_batch": (I, [P, P, S, P]),
+        "bh_verify_each_device": (I, [P, P, S, P, P, S, S, P, P]),
         "bh_verify_batch_device": (I, [P, P, S, P, P, S, S, P, P]),
         "bh_proofs_decode": (I, [P, P, S, P, P, P, P]),
     }
@@ -243,7 +245,7 @@ EXPORTED_SYMBOLS = [
     "bh_mpc_last_miller_ms", "bh_mpc_last_miller_device", "bh_miller_product", "bh_final_exponentiation",
     "bh_verify_batch_device", "bh_proofs_decode", "bh_r1cs_witness", "bh_witness_sizes", "bh_witness_read",
     "bh_srs_fft", "bh_srs_read", "bh_mpc_common_matrix", "bh_mpc_matrix_vector", "bh_mpc_matrix_free",
-    "bh_mpc_parameters", "bh_mpc_last_matrix_ms",
+    "bh_mpc_parameters", "bh_mpc_last_matrix_ms", "bh_final_exponentiation_batch", "bh_verify_each_device",
 ] + [f"bh_mpc_{kind}{who}_{op}" for kind in ("common", "uncommon") for who in ("", "_contrib")
      for op in ("free", "vector", "point", "write", "read")]
 BH_VEC_H, BH_VEC_L, BH_VEC_A, BH_VEC_B_G1, BH_VEC_B_G2 = range(5)
@@ -1477,6 +1479,29 @@ def verify_batch_device(ctx, vk_bytes, proofs, public_inputs, zs):
     return bool(ok.value)
 
 
+def verify_each(ctx, vk_bytes, proofs, public_inputs):
+    """verify_proof of every proof of a list on ctx's device (bh_verify_each_device) ->
+    (statuses, valids): per proof the BH_ERR_* code (0 for a well-formed item) and the verdict that
+    verify_proof gives it; a malformed or invalid proof does not affect the others.  Raises for what
+    is common to all items (the verifying key, the number of inputs); an empty list gives two empty
+    lists without a call (the number of inputs is taken from the first item)."""
+    k = len(proofs)
+    if not k:
+        return [], []
+    vk = np.frombuffer(bytes(vk_bytes), dtype=np.uint8)
+    pf = np.frombuffer(b"".join(bytes(p) for p in proofs) or b"\0", dtype=np.uint8)
+    assert k == 0 or pf.size == 192 * k
+    ni = len(public_inputs[0]) if k else 0
+    assert all(len(row) == ni for row in public_inputs)
+    flat = [x for row in public_inputs for x in row]
+    ins = fr_to_canonical_limbs(flat) if flat else np.zeros((1, 4), dtype=np.uint64)
+    st = np.zeros(max(k, 1), dtype=np.uint32)
+    ok = np.zeros(max(k, 1), dtype=np.uint8)
+    _check(_lib.bh_verify_each_device(ctx.h, _ptr(vk), vk.size, _ptr(pf), _ptr(ins), ni, k, _ptr(st), _ptr(ok)),
+           "verify_each")
+    return [int(x) for x in st[:k]], [bool(x) for x in ok[:k]]
+
+
 def proofs_decode(ctx, proofs):
     """Proof::read of a list of 192-byte proofs on the device (bh_proofs_decode) -> (A, B, C,
     statuses): three Bases of len(proofs) points (G1, G2, G1) and a list of zeros, or, when a
@@ -1522,6 +1547,11 @@ class Verifier:
             return verify_batch(vk_bytes, proofs, inputs, zs)
         return verify_batch_device(ctx, vk_bytes, proofs, inputs, zs)
 
+    def verify_each(self, vk_bytes, ctx):
+        """(statuses, valids) of every queued item on ctx's device (verify_each): the way out that
+        batch.rs:54-60 gives each item once the batch has answered "invalid"."""
+        return verify_each(ctx, vk_bytes, [p for p, _ in self.items], [i for _, i in self.items])
+
 
 def _f12_from_bytes(b):
     c = [int.from_bytes(b[48 * k:48 * k + 48], "big") for k in range(12)]
@@ -1551,6 +1581,17 @@ def final_exponentiation(f):
     out = np.zeros(576, dtype=np.uint8)
     _check(_lib.bh_final_exponentiation(_ptr(src), _ptr(out)), "bh_final_exponentiation")
     return _f12_from_bytes(out.tobytes())
+
+
+def final_exponentiation_batch(ctx, values):
+    """final_exponentiation of every value of a list on ctx's device
+    (bh_final_exponentiation_batch): the same results, value for value."""
+    n = len(values)
+    src = np.frombuffer(b"".join(_f12_to_bytes(f) for f in values) or b"\0", dtype=np.uint8)
+    out = np.zeros(max(576 * n, 1), dtype=np.uint8)
+    _check(_lib.bh_final_exponentiation_batch(ctx.h, _ptr(src), n, _ptr(out)), "bh_final_exponentiation_batch")
+    raw = out.tobytes()
+    return [_f12_from_bytes(raw[576 * i:576 * i + 576]) for i in range(n)]
 
 
 def pairing_product_is_one(ctx, g1_bases, g2_bases):

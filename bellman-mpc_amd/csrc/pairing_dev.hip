@@ -18,6 +18,9 @@
 //   k_f12_product    the lanes' values multiplied by levels in the style of k_rowcol_sum: a thread
 //                    takes the product of <= 8 values read at a stride, until <= 64 remain, which
 //                    the host multiplies with f12_mul.
+//   k_fexp_*         the final exponentiation of every lane's value, in place in the same workspace
+//                    (final_exp_chain.h's program; further down), for bh_final_exponentiation_batch
+//                    and the per-proof verdicts of bh_verify_each_device.
 //
 // State.  f is 12 Fp: it cannot stay in registers beside an Fp2 product's operands, and every
 // output coefficient of a product reads several input coefficients, so f lives in a global
@@ -45,6 +48,7 @@
 #include <algorithm>
 #include <memory>
 
+#include "final_exp_chain.h"
 #include "group_host.h"
 #include "pairing_dev.h"
 
@@ -93,7 +97,7 @@ __device__ DFp2 fp2_inv(const DFp2& x) {
   }
   DFp2 o;
   o.c0 = fe_mul<FpCfg>(x.c0, r);
-  o.c1 = fe_mul<FpCfg>(fe_neg<FpCfg, 2>(x.c1), r);  // x.c1 < 2p at the one call site
+  o.c1 = fe_mul<FpCfg>(fe_neg<FpCfg, 2>(x.c1), r);  // x.c1 < 2p at both call sites
   return o;
 }
 
@@ -298,6 +302,120 @@ __global__ void __launch_bounds__(64) k_f12_product(uint32_t* v, uint32_t* ping,
     for (int w = 0; w < FW; w++) v[(size_t)w * stride + t] = a[(size_t)w * stride + t];
 }
 
+// ---------------------------------------------------------------- final exponentiation
+// final_exp_chain.h's program, one lane per value, in place on FE_SLOTS Fp12 slots of the
+// word-major workspace (word w of slot s of lane l at (s * FW + w) * stride + l).  Every slot
+// holds fully reduced coefficients (< p): each step below stores through F2::reduce or
+// neg_canonical, as f12_mul_dense and the Miller loop do.
+struct FexpArgs {
+  uint32_t* ws;
+  const FeStep* prog;
+  const uint32_t* consts;  // g1_0..5 (24 packed words each), then g2_0..5 (12 each), device Montgomery
+  size_t n, stride;
+};
+
+__device__ __forceinline__ DFp fe_r2() {
+  DFp r2;
+#pragma unroll
+  for (int k = 0; k < FpCfg::N; k++) r2.v[k] = FpCfg::R2[k];
+  return r2;
+}
+
+__global__ void __launch_bounds__(64) k_fexp_steps(FexpArgs A, int lo, int hi) {
+  const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= A.n) return;
+  const size_t slot = (size_t)FW * A.stride;
+#pragma unroll 1
+  for (int s = lo; s < hi; s++) {
+    const FeStep st = A.prog[s];
+    uint32_t* dst = A.ws + st.dst * slot;
+    const uint32_t* a = A.ws + st.a * slot;
+    const uint32_t* b = A.ws + st.b * slot;
+    if (st.op == FE_MUL) {
+      f12_mul_dense(a, lane, b, lane, dst, lane, A.stride);
+    } else if (st.op == FE_CONJ) {
+#pragma unroll 1
+      for (int k = 0; k < 6; k++) {
+        const DFp2 c = ld_fp2(a, A.stride, lane, 24 * k);  // < p
+        st_fp2(dst, A.stride, lane, 24 * k, (k & 1) ? F2::neg_canonical(c) : c);
+      }
+    } else if (st.op == FE_FROB) {
+#pragma unroll 1
+      for (int k = 0; k < 6; k++) {
+        DFp2 c = ld_fp2(a, A.stride, lane, 24 * k);
+        c.c1 = fe_neg<FpCfg, 1>(c.c1);  // c1 < p: p - c1 <= p
+        st_fp2(dst, A.stride, lane, 24 * k, F2::reduce(F2::mul(c, F2::unpack(A.consts + 24 * k))));  // < 2p
+      }
+    } else if (st.op == FE_FROB2) {
+#pragma unroll 1
+      for (int k = 0; k < 6; k++) {
+        const DFp2 c = ld_fp2(a, A.stride, lane, 24 * k);
+        const DFp g = fe_unpack<FpCfg>(A.consts + 144 + 12 * k);
+        st_fp2(dst, A.stride, lane, 24 * k, F2::reduce(DFp2{fe_mul<FpCfg>(c.c0, g), fe_mul<FpCfg>(c.c1, g)}));
+      }
+    } else if (st.op == FE_SCALE_INV) {
+      const DFp2 inv = fp2_inv(ld_fp2(b, A.stride, lane, 0));  // its argument < p; both halves < 2p
+#pragma unroll 1
+      for (int k = 0; k < 6; k++)
+        st_fp2(dst, A.stride, lane, 24 * k, F2::reduce(F2::mul(ld_fp2(a, A.stride, lane, 24 * k), inv)));
+    } else {
+      for (int w = 0; w < FW; w++) dst[(size_t)w * A.stride + lane] = a[(size_t)w * A.stride + lane];
+    }
+  }
+}
+
+// slot 0 of every lane times the value at index 0 of slot 2, through slot 1
+__global__ void __launch_bounds__(64) k_fexp_scale(uint32_t* ws, size_t n, size_t stride) {
+  const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= n) return;
+  const size_t slot = (size_t)FW * stride;
+  f12_mul_dense(ws, lane, ws + 2 * slot, 0, ws + slot, lane, stride);
+  for (int w = 0; w < FW; w++) ws[(size_t)w * stride + lane] = ws[slot + (size_t)w * stride + lane];
+}
+
+// n values of 576 bytes (twelve 48-byte big-endian canonical coefficients) -> slot 0
+__global__ void __launch_bounds__(64) k_fexp_load(const uint32_t* in, uint32_t* ws, size_t n, size_t stride) {
+  const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= n) return;
+#pragma unroll 1
+  for (int j = 0; j < 12; j++) {
+    uint32_t w[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) w[i] = __builtin_bswap32(in[lane * FW + 12 * j + 11 - i]);
+    const DFp x = fe_reduce_full<FpCfg>(fe_mul<FpCfg>(fe_unpack<FpCfg>(w), fe_r2()));
+    fe_pack<FpCfg>(x, w);
+#pragma unroll
+    for (int i = 0; i < 12; i++) ws[(size_t)(12 * j + i) * stride + lane] = w[i];
+  }
+}
+
+// slot 0 -> the same byte form
+__global__ void __launch_bounds__(64) k_fexp_store(const uint32_t* ws, uint32_t* out, size_t n, size_t stride) {
+  const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= n) return;
+#pragma unroll 1
+  for (int j = 0; j < 12; j++) {
+    uint32_t w[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) w[i] = ws[(size_t)(12 * j + i) * stride + lane];
+    // out of Montgomery form: <= p, one conditional subtraction
+    const DFp x = fe_csub<FpCfg, 1>(fe_from_mont<FpCfg>(fe_unpack<FpCfg>(w)));
+    fe_pack<FpCfg>(x, w);
+#pragma unroll
+    for (int i = 0; i < 12; i++) out[lane * FW + 12 * j + 11 - i] = __builtin_bswap32(w[i]);
+  }
+}
+
+// one for every value equal to one, else zero
+__global__ void __launch_bounds__(64) k_fexp_is_one(const uint32_t* ws, uint32_t* out, size_t n, size_t stride) {
+  const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= n) return;
+  uint32_t one[12], diff = 0;
+  fe_pack<FpCfg>(fe_one<FpCfg>(), one);
+  for (int w = 0; w < FW; w++) diff |= ws[(size_t)w * stride + lane] ^ (w < 12 ? one[w] : 0u);
+  out[lane] = diff == 0;
+}
+
 inline unsigned nb64(size_t n) { return (unsigned)((n + 63) / 64); }
 
 // Bits per launch.  All state is in memory, so the split costs one launch each.  At 2^20 pairs a
@@ -331,7 +449,17 @@ int choose_k(bh_ctx* ctx, size_t n) {
   return (int)std::min<size_t>(MILLER_MAX_K, std::max<size_t>(1, (n + resident - 1) / resident));
 }
 
-bh_status miller_chunk(bh_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size_t n, int K, Fp12* out) {
+// The loop's device state of one call.  f: fslots >= 2 Fp12 buffers of FW * stride words each, the
+// first two the loop's double buffer; miller_lanes leaves every lane's value in the first.
+struct MillerWork {
+  DevBuf f, T, S, mask, flag;
+  size_t lanes = 0, stride = 0;
+};
+
+// lane l's value prod_{k < K} f(g1[l K + k], g2[l K + k]) for the lanes of n pairs, left on the
+// device in w->f; returns synchronised.  BH_ERR_PAIRING_DEGENERATE: a step met a zero denominator.
+bh_status miller_lanes(bh_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size_t n, int K, int fslots,
+                       MillerWork* w) {
   MillerArgs A;
   A.g1 = g1;
   A.g2 = g2;
@@ -339,19 +467,19 @@ bh_status miller_chunk(bh_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size
   A.K = K;
   A.lanes = (n + K - 1) / K;
   A.stride = (A.lanes + 63) / 64 * 64;
-  DevBuf f, pong, T, S, mask, flag;
-  BH_TRY_HIP(f.alloc(2 * (size_t)FW * A.stride * 4));
-  BH_TRY_HIP(pong.alloc((size_t)FW * A.stride * 4));
-  BH_TRY_HIP(T.alloc((size_t)K * TW * A.stride * 4));
-  BH_TRY_HIP(S.alloc((size_t)K * SW * A.stride * 4));
-  BH_TRY_HIP(mask.alloc(A.stride * 4));
-  BH_TRY_HIP(flag.alloc(4));
-  A.f = f.as<uint32_t>();
-  A.T = T.as<uint32_t>();
-  A.S = S.as<uint32_t>();
-  A.mask = mask.as<uint32_t>();
-  A.flag = flag.as<uint32_t>();
-  BH_TRY_HIP(hipMemsetAsync(flag.p, 0, 4, ctx->stream));
+  w->lanes = A.lanes;
+  w->stride = A.stride;
+  BH_TRY_HIP(w->f.alloc((size_t)fslots * FW * A.stride * 4));
+  BH_TRY_HIP(w->T.alloc((size_t)K * TW * A.stride * 4));
+  BH_TRY_HIP(w->S.alloc((size_t)K * SW * A.stride * 4));
+  BH_TRY_HIP(w->mask.alloc(A.stride * 4));
+  BH_TRY_HIP(w->flag.alloc(4));
+  A.f = w->f.as<uint32_t>();
+  A.T = w->T.as<uint32_t>();
+  A.S = w->S.as<uint32_t>();
+  A.mask = w->mask.as<uint32_t>();
+  A.flag = w->flag.as<uint32_t>();
+  BH_TRY_HIP(hipMemsetAsync(w->flag.p, 0, 4, ctx->stream));
   hipLaunchKernelGGL(k_miller_init, dim3(nb64(A.lanes)), dim3(64), 0, ctx->stream, A);
   BH_TRY_HIP(hipGetLastError());
   for (int hi = 62; hi >= 0; hi -= MILLER_BITS_PER_LAUNCH) {
@@ -360,24 +488,34 @@ bh_status miller_chunk(bh_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size
     BH_TRY_HIP(hipGetLastError());
   }
   uint32_t hflag = 0;
-  BH_TRY_HIP(hipMemcpyAsync(&hflag, flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+  BH_TRY_HIP(hipMemcpyAsync(&hflag, w->flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
   BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
-  if (hflag) return BH_ERR_PAIRING_DEGENERATE;
-  size_t m = A.lanes;
+  return hflag ? BH_ERR_PAIRING_DEGENERATE : BH_OK;
+}
+
+bh_status miller_chunk(bh_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size_t n, int K, Fp12* out) {
+  MillerWork w;
+  bh_status s = miller_lanes(ctx, g1, g2, n, K, 2, &w);
+  if (s) return s;
+  uint32_t* f = w.f.as<uint32_t>();
+  const size_t stride = w.stride;
+  DevBuf pong;
+  BH_TRY_HIP(pong.alloc((size_t)FW * stride * 4));
+  size_t m = w.lanes;
   while (m > 64) {
     const size_t o = (m + 7) / 8;
-    hipLaunchKernelGGL(k_f12_product, dim3(nb64(o)), dim3(64), 0, ctx->stream, A.f, A.f + (size_t)FW * A.stride,
-                       pong.as<uint32_t>(), A.stride, m, o);
+    hipLaunchKernelGGL(k_f12_product, dim3(nb64(o)), dim3(64), 0, ctx->stream, f, f + (size_t)FW * stride,
+                       pong.as<uint32_t>(), stride, m, o);
     BH_TRY_HIP(hipGetLastError());
     m = o;
   }
-  std::vector<uint32_t> rows((size_t)FW * m), w(FW);
-  BH_TRY_HIP(hipMemcpy2DAsync(rows.data(), m * 4, A.f, A.stride * 4, m * 4, FW, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<uint32_t> rows((size_t)FW * m), wd(FW);
+  BH_TRY_HIP(hipMemcpy2DAsync(rows.data(), m * 4, f, stride * 4, m * 4, FW, hipMemcpyDeviceToHost, ctx->stream));
   BH_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the workspace is freed on return
   Fp12 r = f12_one();
   for (size_t t = 0; t < m; t++) {
-    for (int k = 0; k < FW; k++) w[k] = rows[(size_t)k * m + t];
-    r = f12_mul(r, f12_from_dev_words(w.data()));
+    for (int k = 0; k < FW; k++) wd[k] = rows[(size_t)k * m + t];
+    r = f12_mul(r, f12_from_dev_words(wd.data()));
   }
   *out = r;
   return BH_OK;
@@ -388,6 +526,108 @@ void f12_to_bytes(const Fp12& f, uint8_t out[576]) {
     fp_to_be(f.c[i].c0, out + 96 * i);
     fp_to_be(f.c[i].c1, out + 96 * i + 48);
   }
+}
+
+// host Montgomery (R = 2^384) -> the device's packed words (the canonical value of c * 2^406)
+void fp_to_dev_words(const Fp& x, uint32_t* w) {
+  static const Fp K = [] {
+    uint64_t two[6] = {2, 0, 0, 0, 0, 0}, e[1] = {406}, raw[6];
+    to_int(pow_vartime(from_int<6>(two), e, 1), raw);  // canonical 2^406 mod p
+    Fp out;
+    memcpy(out.v, raw, sizeof raw);
+    return out;
+  }();
+  const Fp t = mul(x, K);  // (c 2^384) (2^406) / 2^384 = c 2^406 mod p, the words themselves
+  memcpy(w, t.v, 48);
+}
+
+// Steps per launch, in units of one dense Fp12 product (36 Fp2 products, about 108 Fp products' worth of
+// work; the inversion step's Fermat ladder counts as four, the coefficient-wise steps as nothing).
+// All state is in memory, so a split costs one launch: 49 launches for the chain.  Measured at 2^14
+// lanes: 1.06 ms per launch; at MILLER_CHUNK lanes, 64 times as many, a launch stays under the
+// library's longest dispatch (k_varbase_mul_win<G2>, 147 ms per 2^20) even if it scaled with the
+// lane count from there.
+constexpr int FEXP_PRODUCTS_PER_LAUNCH = 8;
+
+// The chain in place on slot 0 of ws (FE_SLOTS * FW * stride words), enqueued on ctx->stream; the
+// tables must outlive the enqueued work (the caller synchronises before dropping them).
+struct FexpTables {
+  DevBuf prog, consts;
+  std::vector<std::pair<int, int>> launches;
+};
+
+bh_status fexp_tables(bh_ctx* ctx, FexpTables* t) {
+  const std::vector<FeStep>& p = fe_program();
+  const FeConsts& C = fe_consts();
+  uint32_t cw[6 * 24 + 6 * 12];
+  for (int k = 0; k < 6; k++) {
+    fp_to_dev_words(C.g1[k].c0, cw + 24 * k);
+    fp_to_dev_words(C.g1[k].c1, cw + 24 * k + 12);
+    fp_to_dev_words(C.g2[k], cw + 144 + 12 * k);
+  }
+  BH_TRY_HIP(t->prog.alloc(p.size() * sizeof(FeStep)));
+  BH_TRY_HIP(t->consts.alloc(sizeof cw));
+  BH_TRY_HIP(hipMemcpyAsync(t->prog.p, p.data(), p.size() * sizeof(FeStep), hipMemcpyHostToDevice, ctx->stream));
+  BH_TRY_HIP(hipMemcpyAsync(t->consts.p, cw, sizeof cw, hipMemcpyHostToDevice, ctx->stream));
+  BH_TRY_HIP(hipStreamSynchronize(ctx->stream));  // both sources are about to go away
+  int lo = 0, weight = 0;
+  for (int s = 0; s < (int)p.size(); s++) {
+    weight += p[s].op == FE_MUL ? 1 : p[s].op == FE_SCALE_INV ? 4 : 0;
+    if (weight >= FEXP_PRODUCTS_PER_LAUNCH || s + 1 == (int)p.size()) {
+      t->launches.push_back({lo, s + 1});
+      lo = s + 1;
+      weight = 0;
+    }
+  }
+  return BH_OK;
+}
+
+bh_status fexp_enqueue(bh_ctx* ctx, const FexpTables& t, uint32_t* ws, size_t n, size_t stride) {
+  FexpArgs A;
+  A.ws = ws;
+  A.prog = t.prog.as<FeStep>();
+  A.consts = t.consts.as<uint32_t>();
+  A.n = n;
+  A.stride = stride;
+  for (const auto& l : t.launches) {
+    hipLaunchKernelGGL(k_fexp_steps, dim3(nb64(n)), dim3(64), 0, ctx->stream, A, l.first, l.second);
+    BH_TRY_HIP(hipGetLastError());
+  }
+  return BH_OK;
+}
+
+// a coefficient >= p among the 12 n big-endian 48-byte values
+bool f12_bytes_canonical(const uint8_t* f, size_t n) {
+  uint8_t pb[48];
+  for (int i = 0; i < 48; i++) pb[i] = (uint8_t)(hostc::FP_P[5 - i / 8] >> (8 * (7 - i % 8)));
+  for (size_t i = 0; i < 12 * n; i++)
+    if (memcmp(f + 48 * i, pb, 48) >= 0) return false;
+  return true;
+}
+
+bh_status final_exponentiation_batch(bh_ctx* ctx, const uint8_t* f, size_t n, uint8_t* out) {
+  if (!f12_bytes_canonical(f, n)) return BH_ERR_INVALID_ENCODING;
+  FexpTables t;
+  bh_status s = fexp_tables(ctx, &t);
+  if (s) return s;
+  const size_t chunk = std::min(n, MILLER_CHUNK), stride = (chunk + 63) / 64 * 64;
+  DevBuf io, ws;
+  BH_TRY_HIP(io.alloc(chunk * 576));
+  BH_TRY_HIP(ws.alloc((size_t)FE_SLOTS * FW * stride * 4));
+  for (size_t base = 0; base < n; base += chunk) {
+    const size_t m = std::min(chunk, n - base);
+    BH_TRY_HIP(hipMemcpyAsync(io.p, f + 576 * base, 576 * m, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_fexp_load, dim3(nb64(m)), dim3(64), 0, ctx->stream, io.as<uint32_t>(), ws.as<uint32_t>(), m,
+                       stride);
+    BH_TRY_HIP(hipGetLastError());
+    if ((s = fexp_enqueue(ctx, t, ws.as<uint32_t>(), m, stride))) return s;
+    hipLaunchKernelGGL(k_fexp_store, dim3(nb64(m)), dim3(64), 0, ctx->stream, ws.as<uint32_t>(), io.as<uint32_t>(), m,
+                       stride);
+    BH_TRY_HIP(hipGetLastError());
+    BH_TRY_HIP(hipMemcpyAsync(out + 576 * base, io.p, 576 * m, hipMemcpyDeviceToHost, ctx->stream));
+    BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  return BH_OK;
 }
 
 bh_status miller_product_abi(bh_ctx* ctx, const bh_srs* g1, size_t off1, const bh_srs* g2, size_t off2, size_t n, int K,
@@ -413,6 +653,44 @@ void pairing_kernels(std::vector<KernInfo>& v) {
   v.push_back({"k_miller_init", (const void*)k_miller_init, 64, 0});
   v.push_back({"k_miller_steps", (const void*)k_miller_steps, 64, 0});
   v.push_back({"k_f12_product", (const void*)k_f12_product, 64, 0});
+  v.push_back({"k_fexp_steps", (const void*)k_fexp_steps, 64, 0});
+  v.push_back({"k_fexp_scale", (const void*)k_fexp_scale, 64, 0});
+  v.push_back({"k_fexp_load", (const void*)k_fexp_load, 64, 0});
+  v.push_back({"k_fexp_store", (const void*)k_fexp_store, 64, 0});
+  v.push_back({"k_fexp_is_one", (const void*)k_fexp_is_one, 64, 0});
+}
+
+bh_status pairing_each_is_one(bh_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size_t lanes, int K,
+                              const Fp12& scale, uint32_t* verdict) {
+  if (K < 1 || K > MILLER_MAX_K) return BH_ERR_INVALID_ARGUMENT;
+  if (!lanes) return BH_OK;
+  FexpTables t;
+  bh_status s = fexp_tables(ctx, &t);
+  if (s) return s;
+  uint32_t sw[FW];
+  for (int i = 0; i < 6; i++) {
+    fp_to_dev_words(scale.c[i].c0, sw + 24 * i);
+    fp_to_dev_words(scale.c[i].c1, sw + 24 * i + 12);
+  }
+  DevBuf ok;
+  BH_TRY_HIP(ok.alloc(std::min(lanes, MILLER_CHUNK) * 4));
+  for (size_t base = 0; base < lanes; base += MILLER_CHUNK) {
+    const size_t m = std::min(MILLER_CHUNK, lanes - base);
+    MillerWork w;
+    if ((s = miller_lanes(ctx, g1 + base * K * 24, g2 + base * K * 48, m * K, K, FE_SLOTS, &w))) return s;
+    uint32_t* ws = w.f.as<uint32_t>();
+    // the constant at index 0 of slot 2, which the chain overwrites only later
+    BH_TRY_HIP(hipMemcpy2DAsync(ws + 2 * (size_t)FW * w.stride, w.stride * 4, sw, 4, 4, FW, hipMemcpyHostToDevice,
+                                ctx->stream));
+    hipLaunchKernelGGL(k_fexp_scale, dim3(nb64(m)), dim3(64), 0, ctx->stream, ws, m, w.stride);
+    BH_TRY_HIP(hipGetLastError());
+    if ((s = fexp_enqueue(ctx, t, ws, m, w.stride))) return s;
+    hipLaunchKernelGGL(k_fexp_is_one, dim3(nb64(m)), dim3(64), 0, ctx->stream, ws, ok.as<uint32_t>(), m, w.stride);
+    BH_TRY_HIP(hipGetLastError());
+    BH_TRY_HIP(hipMemcpyAsync(verdict + base, ok.p, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    BH_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the workspace is freed at the end of the pass
+  }
+  return BH_OK;
 }
 
 bh_status miller_product_device(bh_ctx* ctx, const bh_srs* g1, size_t off1, const bh_srs* g2, size_t off2, size_t n,
@@ -454,6 +732,26 @@ bh_status bh_final_exponentiation(const uint8_t f[576], uint8_t out[576]) {
       return BH_ERR_INVALID_ENCODING;  // a coefficient >= p
   f12_to_bytes(final_exponentiation(a), out);
   return BH_OK;
+}
+
+bh_status bh_selftest_final_exponentiation_chain(const uint8_t f[576], uint8_t out[576]) {
+  if (!f || !out) return BH_ERR_INVALID_ARGUMENT;
+  Fp12 a;
+  for (int i = 0; i < 6; i++)
+    if (!fp_from_be(f + 96 * i, &a.c[i].c0) || !fp_from_be(f + 96 * i + 48, &a.c[i].c1))
+      return BH_ERR_INVALID_ENCODING;
+  f12_to_bytes(fe_chain_host(a), out);
+  return BH_OK;
+}
+
+bh_status bh_final_exponentiation_batch(bh_ctx* ctx, const uint8_t* f, size_t n, uint8_t* out) {
+  if (!ctx || (n && (!f || !out))) return BH_ERR_INVALID_ARGUMENT;
+  if (!n) return BH_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  BH_TRY_HIP(hipSetDevice(ctx->device));
+  bh_status s = scratch_check(ctx);
+  if (s) return s;
+  return final_exponentiation_batch(ctx, f, n, out);
 }
 
 }  // extern "C"

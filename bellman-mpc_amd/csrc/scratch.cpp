@@ -24,6 +24,7 @@
 #include "proofs_dev.h"
 #include "r1cs.h"
 #include "varbase.h"
+#include "verify_each.h"
 
 namespace bh {
 
@@ -94,6 +95,7 @@ bh_status scratch_report(bh_ctx* ctx, uint64_t out[10], std::string* worst) {
   group_fft_kernels(ks);
   pairing_kernels(ks);
   proofs_kernels(ks);
+  verify_each_kernels(ks);
   const uint64_t cus = (uint64_t)std::max(prop.multiProcessorCount, 1);
   const uint64_t slots_per_cu = 32;  // KFD max_slots_scratch_cu (profiles/r03_kfd_queue_props.txt)
   // per queue: at the scratch-slot bound (what the runtime may reserve for a large dispatch:

@@ -32,6 +32,12 @@ bh_status varbase_mul(bh_ctx* ctx, const bh_srs* in, const uint32_t* d_sc, int s
 template <class C>
 hipError_t varbase_mul_chunk(const uint32_t* d_pts, const uint32_t* d_sc, int stride, size_t k, int W, int top_biased,
                              void* d_xyzz, void* d_scr, uint32_t* d_table, uint32_t* d_flag, hipStream_t st);
+// The table that multiplication reads, alone: 1P .. 8P of the k points of d_pts as packed affine
+// records, digit-major (record d k + i holds (d + 1) P_i), enqueued on st.  No point may be the
+// identity or of order <= 8.  Workspace as above.
+template <class C>
+hipError_t varbase_multiples_table(const uint32_t* d_pts, size_t k, void* d_xyzz, void* d_scr, uint32_t* d_table,
+                                   hipStream_t st);
 constexpr size_t VB_WIN_CHUNK = (size_t)1 << 18;  // points per chunk of the windowed multiplication
 // out[i] = in[lo2 + i] - in[lo1 + i], i < n; a difference that is the identity:
 // BH_ERR_UNEXPECTED_IDENTITY

@@ -193,13 +193,23 @@ struct VbScratch {
 }  // namespace
 
 template <class C>
+hipError_t varbase_multiples_table(const uint32_t* d_pts, size_t k, void* d_xyzz, void* d_scr, uint32_t* d_table,
+                                   hipStream_t st) {
+  hipLaunchKernelGGL(k_varbase_multiples<C>, dim3(nb(k, 256)), dim3(256), 0, st, d_pts, k,
+                     reinterpret_cast<typename C::P*>(d_xyzz));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return normalize_batch<C>(d_xyzz, 8 * k, d_scr, d_table, st);
+}
+template hipError_t varbase_multiples_table<G1Ops>(const uint32_t*, size_t, void*, void*, uint32_t*, hipStream_t);
+template hipError_t varbase_multiples_table<G2Ops>(const uint32_t*, size_t, void*, void*, uint32_t*, hipStream_t);
+
+template <class C>
 hipError_t varbase_mul_chunk(const uint32_t* d_pts, const uint32_t* d_sc, int stride, size_t k, int W, int top_biased,
                              void* d_xyzz, void* d_scr, uint32_t* d_table, uint32_t* d_flag, hipStream_t st) {
   using P = typename C::P;
-  hipLaunchKernelGGL(k_varbase_multiples<C>, dim3(nb(k, 256)), dim3(256), 0, st, d_pts, k, reinterpret_cast<P*>(d_xyzz));
-  hipError_t e = hipGetLastError();
+  hipError_t e = varbase_multiples_table<C>(d_pts, k, d_xyzz, d_scr, d_table, st);
   if (e != hipSuccess) return e;
-  if ((e = normalize_batch<C>(d_xyzz, 8 * k, d_scr, d_table, st)) != hipSuccess) return e;
   hipLaunchKernelGGL(k_varbase_mul_win<C>, dim3(nb(k, 256)), dim3(256), 0, st, d_table, d_sc, stride, k, W, top_biased,
                      reinterpret_cast<P*>(d_xyzz), d_flag);
   return hipGetLastError();

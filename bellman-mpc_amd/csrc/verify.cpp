@@ -11,7 +11,8 @@
 // (groth16/mod.rs:50-103: compressed, torsion-checked, identity rejected), verifying keys like
 // VerifyingKey::read (mod.rs:174-222).  bh_verify_proof and bh_verify_batch are host-only code: no
 // device is needed.  bh_verify_batch_device, at the end, is the batch verifier with its per-proof
-// work on the device and the same statuses and verdicts.
+// work on the device and the same statuses and verdicts; bh_verify_each_device is verify_proof of
+// every proof of a list, all of it on the device but the verifying key's own pairing value.
 #include <string.h>
 
 #include <algorithm>
@@ -22,6 +23,7 @@
 #include "pairing_dev.h"
 #include "proofs_dev.h"
 #include "varbase.h"
+#include "verify_each.h"
 
 using namespace bh;
 
@@ -422,6 +424,62 @@ bh_status bh_verify_batch_device(bh_ctx* ctx, const uint8_t* vk_bytes, size_t vk
                                   {neg_pt(jac_to_affine(jac_mul(jac_from_affine(vk.alpha_g1), yw, 4))), vk.beta_g2}};
   f = f12_mul(f, multi_miller_loop(rest));
   *valid = f12_is_one(final_exponentiation(f)) ? 1 : 0;
+  return BH_OK;
+}
+
+// bh_verify_proof of each of k proofs, the proofs' work on the device: Proof::read
+// (proofs_dev.hip), acc_j and the lanes' pairs (verify_each.hip), then per lane the three Miller
+// loops f(A_j, B_j) f(-acc_j, gamma) f(-C_j, delta), the product by f(-alpha, beta) -- the one value
+// the host computes, once per call --, the final exponentiation and the comparison with one
+// (pairing_dev.hip).  The G1 points are negated where bh_verify_proof negates gamma and delta:
+// e(-P, Q) = e(P, -Q), so each lane's value after the final exponentiation is the host's.
+// A lane whose proof failed to decode runs on generators (proofs_decode_device) and one with an
+// input >= r on a zero scalar; their verdicts are discarded.
+bh_status bh_verify_each_device(bh_ctx* ctx, const uint8_t* vk_bytes, size_t vk_len, const uint8_t* proofs,
+                                const uint64_t* inputs, size_t num_inputs, size_t k, uint32_t* status, uint8_t* valid) {
+  if (!ctx || !vk_bytes || (k && (!proofs || !status || !valid)) || (k && num_inputs && !inputs))
+    return BH_ERR_INVALID_ARGUMENT;
+  Vk vk;
+  bh_status s = vk_read(vk_bytes, vk_len, &vk);
+  if (s) return s;
+  if (num_inputs + 1 != vk.ic.size()) return BH_ERR_INVALID_ARGUMENT;
+  if (!k) return BH_OK;
+  std::vector<uint32_t> st, ok(k);
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    BH_TRY_HIP(hipSetDevice(ctx->device));
+    if ((s = scratch_check(ctx))) return s;
+    bh_srs pa, pb, pc;
+    if ((s = proofs_decode_device(ctx, proofs, k, &st, &pa, &pb, &pc))) return s;
+    std::vector<uint64_t> x(inputs, inputs + 4 * k * num_inputs);
+    for (size_t j = 0; j < k; j++)
+      for (size_t i = 0; i < num_inputs; i++) {
+        uint64_t* xi = &x[4 * (j * num_inputs + i)];
+        if (canonical_ok(xi)) continue;
+        if (!st[j]) st[j] = BH_ERR_INVALID_ARGUMENT;  // the proof's own status comes first
+        memset(xi, 0, 32);
+      }
+    DevBuf g1, g2;
+    if ((s = verify_each_pairs(ctx, pa, pb, pc, vk.ic.data(), vk.ic.size(), vk.gamma_g2, vk.delta_g2, x.data(), k, &g1,
+                               &g2)))
+      return s;
+    const Fp12 scale = multi_miller_loop({{neg_pt(vk.alpha_g1), vk.beta_g2}});
+    s = pairing_each_is_one(ctx, g1.as<uint32_t>(), g2.as<uint32_t>(), k, 3, scale, ok.data());
+  }
+  if (s == BH_ERR_PAIRING_DEGENERATE) {
+    // a zero denominator: no subgroup-checked B, gamma or delta causes one, but no verdict may rest on that
+    for (size_t j = 0; j < k; j++) {
+      int v = 0;
+      status[j] = bh_verify_proof(vk_bytes, vk_len, proofs + 192 * j, inputs + 4 * j * num_inputs, num_inputs, &v);
+      valid[j] = (uint8_t)v;
+    }
+    return BH_OK;
+  }
+  if (s) return s;
+  for (size_t j = 0; j < k; j++) {
+    status[j] = st[j];
+    valid[j] = (!st[j] && ok[j]) ? 1 : 0;
+  }
   return BH_OK;
 }
 

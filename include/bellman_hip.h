@@ -658,6 +658,14 @@ int bh_mpc_last_miller_device(void);
 bh_status bh_miller_product(bh_ctx* ctx, const bh_srs* g1, size_t off1, const bh_srs* g2, size_t off2, size_t n,
                             uint8_t out[576]);
 bh_status bh_final_exponentiation(const uint8_t f[576], uint8_t out[576]);
+/* bh_final_exponentiation of n values on the context's device: f and out hold n x 576 bytes in the
+ * encoding above, and out[i] equals bh_final_exponentiation(f[i]) byte for byte for every canonical
+ * input (zero gives zero).  The verifier's final step (verifier.rs:23-62 compares one such value
+ * per proof), computed with the exponent (p^12 - 1) / r split into its easy part and a short
+ * addition chain for the hard part instead of the host's square-and-multiply ladder.
+ * BH_ERR_INVALID_ENCODING: a coefficient >= p in any value; nothing is written then.  n = 0: BH_OK.
+ * out may be f. */
+bh_status bh_final_exponentiation_batch(bh_ctx* ctx, const uint8_t* f, size_t n, uint8_t* out);
 
 /* ---- batch verification on the device (verifier/batch.rs:95-169).
  * bh_verify_batch_device: for every input the status and *valid of bh_verify_batch, with the
@@ -674,6 +682,28 @@ bh_status bh_final_exponentiation(const uint8_t f[576], uint8_t out[576]);
 bh_status bh_verify_batch_device(bh_ctx* ctx, const uint8_t* vk, size_t vk_len, const uint8_t* proofs,
                                  const uint64_t* inputs, size_t num_inputs, size_t k, const uint64_t* z,
                                  int* valid);
+/* ---- every proof of a list on the device (verifier.rs:23-62 per item).  The batch verifier above
+ * answers for the whole batch and loses "the ability to easily pinpoint failing proofs"
+ * (verifier/batch.rs:3-8); the reference gives every item Item::verify_single "for implementing
+ * fallback logic when batch verification fails" (batch.rs:54-60).  This is that fallback for all k
+ * items at once: for every j < k, status[j] and valid[j] are what
+ *   bh_verify_proof(vk, vk_len, proofs + 192 j, inputs + 4 j num_inputs, num_inputs, &v)
+ * returns and sets -- proof j's decode status first, in the order A, B, C; then an input >= r:
+ * BH_ERR_INVALID_ARGUMENT; valid[j] = 0 whenever status[j] is non-zero -- and one malformed or
+ * invalid proof does not touch the others.  The return value reports only what all items share: a
+ * null pointer, the verifying key's own status, num_inputs + 1 != ic length
+ * (BH_ERR_INVALID_ARGUMENT) and failures of the run; k = 0 is BH_OK.  status: k words, valid: k
+ * bytes.  On the device: Proof::read, acc_j = ic_0 + sum_i x_ji ic_i, per proof the Miller loops
+ * f(A_j, B_j) f(-acc_j, gamma) f(-C_j, delta) (G1 points negated where bh_verify_proof negates
+ * gamma and delta: the pairing values are the same), the product by f(-alpha, beta), which the
+ * host computes once per call, the final exponentiation (bh_final_exponentiation_batch's kernels)
+ * and the comparison with one; k words come back.  There is no size switch inside: the caller
+ * chooses between this and a loop over bh_verify_proof.  Should a Miller step report
+ * BH_ERR_PAIRING_DEGENERATE (no subgroup-checked B, gamma or delta causes that), every item is
+ * answered by bh_verify_proof. */
+bh_status bh_verify_each_device(bh_ctx* ctx, const uint8_t* vk, size_t vk_len, const uint8_t* proofs,
+                                const uint64_t* inputs, size_t num_inputs, size_t k, uint32_t* status,
+                                uint8_t* valid);
 /* Proof::read of k proofs (192 bytes each: compressed A, B, C) on the device, each point as the host
  * verifier decodes it: compression flag clear, infinity flag set, a coordinate >= p (the three flag
  * bits are masked on a point's first 48 bytes only), x^3 + b not a square: BH_ERR_INVALID_ENCODING;
