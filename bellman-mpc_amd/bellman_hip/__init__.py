@@ -190,6 +190,9 @@ def _load():
         "bh_mpc_common_contribute": (I, [P, P, P, P, P, P]),
         "bh_mpc_common_verify": (I, [P, P, P, P, P, P]),
         "bh_mpc_common_h_basis": (I, [P, P, S, P, P]),
+        "bh_mpc_common_check": (I, [P, P, P, P, P]),
+        "bh_mpc_common_verify_structure": (I, [P, P, P, P, P, P, P]),
+        "bh_mpc_last_check_ms": (None, [P]),
         "bh_mpc_common_len": (S, [P]),
         "bh_mpc_uncommon_initial": (I, [P, P, P, P, P, P, P, P]),
         "bh_mpc_uncommon_contribute": (I, [P, P, P, P, P]),
@@ -246,6 +249,7 @@ EXPORTED_SYMBOLS = [
     "bh_verify_batch_device", "bh_proofs_decode", "bh_r1cs_witness", "bh_witness_sizes", "bh_witness_read",
     "bh_srs_fft", "bh_srs_read", "bh_mpc_common_matrix", "bh_mpc_matrix_vector", "bh_mpc_matrix_free",
     "bh_mpc_parameters", "bh_mpc_last_matrix_ms", "bh_final_exponentiation_batch", "bh_verify_each_device",
+    "bh_mpc_common_check", "bh_mpc_common_verify_structure", "bh_mpc_last_check_ms",
 ] + [f"bh_mpc_{kind}{who}_{op}" for kind in ("common", "uncommon") for who in ("", "_contrib")
      for op in ("free", "vector", "point", "write", "read")]
 BH_VEC_H, BH_VEC_L, BH_VEC_A, BH_VEC_B_G1, BH_VEC_B_G2 = range(5)
@@ -1662,6 +1666,11 @@ class Comm:
  BH_MPC_BETA_TAU_G2) = range(6)
 BH_MPC_KIN_G1, BH_MPC_KIN_G2, BH_MPC_KOUT_G1, BH_MPC_KOUT_G2, BH_MPC_H_G1, BH_MPC_H_G2 = range(6)
 BH_MPC_MATRIX_A, BH_MPC_MATRIX_B_G1, BH_MPC_MATRIX_B_G2 = 6, 7, 8
+# bits of bh_mpc_common_check's / bh_mpc_common_verify_structure's mask
+(BH_MPC_CHECK_FIRST, BH_MPC_CHECK_ALPHA, BH_MPC_CHECK_BETA, BH_MPC_CHECK_POWERS, BH_MPC_CHECK_TAU_G2,
+ BH_MPC_CHECK_ALPHA_TAU, BH_MPC_CHECK_ALPHA_TAU_G2, BH_MPC_CHECK_BETA_TAU, BH_MPC_CHECK_BETA_TAU_G2,
+ BH_MPC_CHECK_LENGTHS, BH_MPC_CHECK_ALPHA_RATIO, BH_MPC_CHECK_BETA_RATIO, BH_MPC_CHECK_TAU_RATIO) = (
+    1 << k for k in range(13))
 
 
 class _MpcHandle:
@@ -1756,6 +1765,15 @@ class CommonParamterInStorage(_MpcStorage):
         _check(_lib.bh_mpc_common_matrix(self.ctx.h, self.h, r1cs.h, ctypes.byref(h)), "bh_mpc_common_matrix")
         return CommonParamterMatrix(self.ctx, h)
 
+    def check(self, rho=None):
+        """bh_mpc_common_check: the mask of failed structure equations (BH_MPC_CHECK_*), 0 for a
+        well-formed storage.  rho: one nonzero scalar below r (default: a fresh random one)."""
+        valid, mask = ctypes.c_int(), ctypes.c_uint32()
+        _check(_lib.bh_mpc_common_check(self.ctx.h, self.h, _ptr(_rho_words(rho)), ctypes.byref(valid),
+                                        ctypes.byref(mask)), "bh_mpc_common_check")
+        assert bool(valid.value) == (mask.value == 0)
+        return mask.value
+
 
 class CommonParamterMatrix:
     """mpc.rs:597-645 for one circuit, device-resident: kin and kout (beta A_j + alpha B_j + C_j of the
@@ -1840,6 +1858,30 @@ def verify_common_paramter(ctx, storage, new_paramter, z=None):
     _check(_lib.bh_mpc_common_verify(ctx.h, storage.h, new_paramter.h, _ptr(_z_words(z)), ctypes.byref(valid),
                                      ctypes.byref(h)), "bh_mpc_common_verify")
     return CommonParamterInStorage(ctx, h) if valid.value else None
+
+
+def _rho_words(rho):
+    import secrets
+    return fr_canonical_words(secrets.randbelow(R_MODULUS - 1) + 1 if rho is None else rho)
+
+
+def verify_common_paramter_structure(ctx, storage, new_paramter, rho=None, return_mask=False):
+    """bh_mpc_common_verify_structure: like verify_common_paramter for a WELL-FORMED storage (the
+    initial one, one whose check() returned 0, or one this function returned), with a constant number
+    of pairings and the tau lists checked.  The next storage or None; (next, mask) on request."""
+    valid, mask, h = ctypes.c_int(), ctypes.c_uint32(), ctypes.c_void_p()
+    _check(_lib.bh_mpc_common_verify_structure(ctx.h, storage.h, new_paramter.h, _ptr(_rho_words(rho)),
+                                               ctypes.byref(valid), ctypes.byref(mask), ctypes.byref(h)),
+           "bh_mpc_common_verify_structure")
+    nxt = CommonParamterInStorage(ctx, h) if valid.value else None
+    return (nxt, mask.value) if return_mask else nxt
+
+
+def last_check_ms():
+    """(weights and multiexps, pairings): wall ms of this thread's last structure check."""
+    out = (ctypes.c_double * 2)()
+    _lib.bh_mpc_last_check_ms(out)
+    return tuple(out)
 
 
 def initial_uncommon_paramters(ctx, front_g1, front_g2=None, back_g1=None, back_g2=None, h_g1=None, h_g2=None):

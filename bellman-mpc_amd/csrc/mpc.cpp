@@ -12,7 +12,10 @@
 // point pair and a TauParameterPair (a list of ParameterPairs) for each vector pair.  The player's
 // side is varbase.hip's per-element multiplication for the results and crs.hip's fixed-base path
 // for the "mine" lists; the verifier batches the reference's per-element pairing checks with the
-// caller's random z_i over verify.cpp's Miller loop.
+// caller's random z_i over verify.cpp's Miller loop.  The structure check
+// (bh_mpc_common_check, bh_mpc_common_verify_structure) is not in the
+// reference: it shows that a round-one storage is a power sequence, with the multiexp, the
+// power-scalar kernel and the host pairing that are already here.
 #include <stdlib.h>
 #include <string.h>
 
@@ -462,10 +465,109 @@ struct CtxLock {
 thread_local double g_miller_ms = 0;
 thread_local int g_miller_device = 0;
 thread_local double g_matrix_ms[3] = {0, 0, 0};
+thread_local double g_check_ms[2] = {0, 0};
 
 double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
+
+// ---------------------------------------------------------------- the structure check
+// What bh_mpc_common_check looks at: a storage's own fields, or a contribution's results (its
+// to_storage_format(), mpc.rs:381-394) before they are cloned.
+struct CheckView {
+  AffinePt<Fp> p1[2];
+  AffinePt<Fp2> p2[2];
+  const bh_srs* v[6];
+};
+CheckView view_of(const MpcStorage* st) {
+  CheckView w;
+  for (int k = 0; k < 2; k++) {
+    w.p1[k] = st->p1[k];
+    w.p2[k] = st->p2[k];
+  }
+  for (int k = 0; k < 6; k++) w.v[k] = st->v[k].get();
+  return w;
+}
+CheckView view_of(const MpcContrib* c) {
+  CheckView w;
+  for (int k = 0; k < 2; k++) {
+    w.p1[k] = c->pp[k].r1;
+    w.p2[k] = c->pp[k].r2;
+  }
+  for (int k = 0; k < 6; k++) w.v[k] = c->res[k].get();
+  return w;
+}
+
+struct Equation {  // `bit` (a BH_MPC_CHECK_* constant) is set unless the product of the pairs is one
+  uint32_t bit;
+  std::vector<Pair> pairs;
+};
+
+template <class T>
+bool same_bytes(const AffinePt<T>& a, const AffinePt<T>& b) {
+  uint8_t x[HostOfField<T>::WIRE], y[HostOfField<T>::WIRE];
+  to_uncompressed(a, x);
+  to_uncompressed(b, y);
+  return a.infinity == b.infinity && !memcmp(x, y, sizeof x);
+}
+
+// Equations 0-8 of bh_mpc_common_check on w, whose six vectors have one
+// length, with the weights rho^i; `more` joins the nine pairing equations on the pool.  The sums
+// are msm_device's over the weights varbase_power_scalars writes; the shifted sum R is the tau
+// vector from element 1 under the weights from index 0.  ms[0]: weights and multiexps, ms[1]:
+// pairings.
+bh_status structure_mask(bh_ctx* ctx, const CheckView& w, const uint64_t rho[4], std::vector<Equation> more,
+                         uint32_t* mask, double ms[2]) {
+  const size_t len = w.v[0]->n;
+  const AffinePt<Fp> g1 = g1_gen();
+  const AffinePt<Fp2> g2 = g2_gen(), ng2 = pt_neg(g2);
+  uint32_t m = 0;
+  std::vector<Equation> eq = std::move(more);
+  eq.push_back({BH_MPC_CHECK_ALPHA, {{w.p1[0], ng2}, {g1, w.p2[0]}}});
+  eq.push_back({BH_MPC_CHECK_BETA, {{w.p1[1], ng2}, {g1, w.p2[1]}}});
+  auto t0 = std::chrono::steady_clock::now();
+  if (len) {
+    std::vector<AffinePt<Fp>> t1;
+    std::vector<AffinePt<Fp2>> t2;
+    bh_status s;
+    if ((s = download_points<G1Host>(*w.v[0], 1, &t1))) return s;
+    if ((s = download_points<G2Host>(*w.v[1], std::min<size_t>(len, 2), &t2))) return s;
+    if (!same_bytes(t1[0], g1) || !same_bytes(t2[0], g2)) m |= BH_MPC_CHECK_FIRST;
+    DevBuf d_w;
+    const uint64_t one[4] = {1, 0, 0, 0};
+    if ((s = varbase_power_scalars(ctx, len, one, rho, 0, &d_w))) return s;
+    AffinePt<Fp> s1[3];
+    AffinePt<Fp2> s2[3];
+    for (int j = 0; j < 3; j++) {
+      if ((s = msm(ctx, w.v[2 * j], d_w.as<uint32_t>(), &s1[j]))) return s;
+      if ((s = msm(ctx, w.v[2 * j + 1], d_w.as<uint32_t>(), &s2[j]))) return s;
+    }
+    if (len >= 2) {
+      Jac<Fp> l, r;
+      if ((s = msm_device<G1Host>(ctx, w.v[0], 0, d_w.as<uint32_t>(), len - 1, nullptr, &l, nullptr))) return s;
+      if ((s = msm_device<G1Host>(ctx, w.v[0], 1, d_w.as<uint32_t>(), len - 1, nullptr, &r, nullptr))) return s;
+      eq.push_back({BH_MPC_CHECK_POWERS, {{jac_to_affine(r), ng2}, {jac_to_affine(l), t2[1]}}});
+    }
+    eq.push_back({BH_MPC_CHECK_TAU_G2, {{s1[0], ng2}, {g1, s2[0]}}});
+    const uint32_t by_scalar[3] = {0, BH_MPC_CHECK_ALPHA_TAU, BH_MPC_CHECK_BETA_TAU};
+    const uint32_t in_g2[3] = {0, BH_MPC_CHECK_ALPHA_TAU_G2, BH_MPC_CHECK_BETA_TAU_G2};
+    for (int j = 1; j < 3; j++) {
+      eq.push_back({by_scalar[j], {{s1[j], ng2}, {s1[0], w.p2[j - 1]}}});
+      eq.push_back({in_g2[j], {{s1[j], ng2}, {g1, s2[j]}}});
+    }
+  }
+  ms[0] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  std::vector<char> bad(eq.size(), 0);  // every equation is evaluated: the mask is complete
+  ctx_pool(ctx).parallel_for((int)eq.size(), [&](int k) { bad[k] = !pairing_product_is_one(eq[k].pairs); });
+  for (size_t k = 0; k < eq.size(); k++)
+    if (bad[k]) m |= eq[k].bit;
+  ms[1] = ms_since(t0);
+  *mask = m;
+  return BH_OK;
+}
+
+bool check_weight(const uint64_t* rho) { return rho && scalar_below_r(rho) && !scalar_is_zero(rho); }
 
 }  // namespace
 
@@ -540,6 +642,61 @@ bh_status bh_mpc_common_verify(bh_ctx* ctx, const bh_mpc_common* st, const bh_mp
     if ((s = verify_tau_pair(ctx, st, c, j, d_z.as<uint32_t>(), nbits, &ok, &g_miller_ms, &g_miller_device)))
       return s;
   if (!ok) return BH_OK;
+  if ((s = to_storage(ctx, c, next))) return s;
+  *valid = 1;
+  return BH_OK;
+}
+
+// The storage is a power sequence: DESIGN.md section 16
+bh_status bh_mpc_common_check(bh_ctx* ctx, const bh_mpc_common* st, const uint64_t rho[4], int* valid,
+                              uint32_t* failed) {
+  if (!ctx || !st || !valid || !check_weight(rho) || st->ctx->device != ctx->device) return BH_ERR_INVALID_ARGUMENT;
+  *valid = 0;
+  if (failed) *failed = 0;
+  MPC_ENTER(ctx);
+  uint32_t mask = 0;
+  g_check_ms[0] = g_check_ms[1] = 0;
+  if (bh_status s = structure_mask(ctx, view_of(st), rho, {}, &mask, g_check_ms)) return s;
+  if (failed) *failed = mask;
+  *valid = mask == 0;
+  return BH_OK;
+}
+
+// A contribution to a well-formed storage: three single-element ratio proofs (the first equation
+// of verify_new_paramter, mpc.rs:787-804) and the structure check of the result
+bh_status bh_mpc_common_verify_structure(bh_ctx* ctx, const bh_mpc_common* st, const bh_mpc_common_contrib* c,
+                                         const uint64_t rho[4], int* valid, uint32_t* failed,
+                                         bh_mpc_common** next) {
+  if (!ctx || !st || !c || !valid || !next || !check_weight(rho)) return BH_ERR_INVALID_ARGUMENT;
+  if (st->ctx->device != ctx->device || c->ctx->device != ctx->device) return BH_ERR_INVALID_ARGUMENT;
+  *valid = 0;
+  *next = nullptr;
+  if (failed) *failed = 0;
+  MPC_ENTER(ctx);
+  g_check_ms[0] = g_check_ms[1] = 0;
+  const size_t len = st->v[0]->n;
+  for (int k = 0; k < 6; k++)
+    if (c->res[k]->n != len || c->mine[k]->n != len) {
+      if (failed) *failed = BH_MPC_CHECK_LENGTHS;
+      return BH_OK;
+    }
+  const AffinePt<Fp2> ng2 = pt_neg(g2_gen());
+  std::vector<Equation> ratio;
+  ratio.push_back({BH_MPC_CHECK_ALPHA_RATIO, {{c->pp[0].r1, ng2}, {st->p1[0], c->pp[0].m2}}});
+  ratio.push_back({BH_MPC_CHECK_BETA_RATIO, {{c->pp[1].r1, ng2}, {st->p1[1], c->pp[1].m2}}});
+  bh_status s;
+  if (len >= 2) {
+    std::vector<AffinePt<Fp>> o1, r1;
+    std::vector<AffinePt<Fp2>> m2;
+    if ((s = download_points<G1Host>(*st->v[0], 2, &o1)) || (s = download_points<G1Host>(*c->res[0], 2, &r1)) ||
+        (s = download_points<G2Host>(*c->mine[1], 2, &m2)))
+      return s;
+    ratio.push_back({BH_MPC_CHECK_TAU_RATIO, {{r1[1], ng2}, {o1[1], m2[1]}}});
+  }
+  uint32_t mask = 0;
+  if ((s = structure_mask(ctx, view_of(c), rho, std::move(ratio), &mask, g_check_ms))) return s;
+  if (failed) *failed = mask;
+  if (mask) return BH_OK;
   if ((s = to_storage(ctx, c, next))) return s;
   *valid = 1;
   return BH_OK;
@@ -844,6 +1001,10 @@ bh_status bh_mpc_parameters(bh_ctx* ctx, const bh_mpc_common* round1, const bh_m
 // how many of its vector pairs ran them on the device
 void bh_mpc_last_matrix_ms(double out[3]) {
   for (int k = 0; k < 3; k++) out[k] = g_matrix_ms[k];
+}
+// wall time (ms) of this thread's last structure check: the weights and multiexps, the pairings
+void bh_mpc_last_check_ms(double out[2]) {
+  for (int k = 0; k < 2; k++) out[k] = g_check_ms[k];
 }
 double bh_mpc_last_miller_ms(void) { return g_miller_ms; }
 int bh_mpc_last_miller_device(void) { return g_miller_device; }

@@ -28,6 +28,8 @@
  *   bh_srs_fft             EvaluationDomain<Point<G>>::fft / ifft   domain.rs:81-99, 192-228
  *   bh_mpc_common_matrix   CommonParamterInStorage::matrix, for any circuit   groth16/mpc.rs:597-645
  *   bh_mpc_parameters      generate_parameters_mpc        groth16/generator.rs:163-237
+ *   bh_mpc_common_check / _verify_structure
+ *                          the power-sequence check of a round-one storage (not in the reference)
  *
  * Conventions
  *   - Plain pointers and sizes only; the caller owns every host buffer and the
@@ -504,7 +506,9 @@ bh_status bh_srs_fft(bh_ctx* ctx, const bh_srs* in, int inverse, bh_srs** out);
  *                             the reference accepts is accepted, one it rejects is accepted with
  *                             probability about 2^-120.  Like the reference, whose
  *                             check of the tau list is commented out (mpc.rs:831-840), it checks alpha,
- *                             beta, alpha_mul_tau, beta_mul_tau and the lengths.
+ *                             beta, alpha_mul_tau, beta_mul_tau and the lengths.  It does not show that
+ *                             either storage is a power sequence: run bh_mpc_common_check on a storage
+ *                             of unknown origin first.
  *   bh_mpc_common_h_basis     the matrixed_h part of matrix (mpc.rs:631-635): tau[n + i] - tau[i],
  *                             i < n, in both groups; 2n > len: BH_ERR_INVALID_ARGUMENT.  The rest of
  *                             matrix is bh_mpc_common_matrix, further down.
@@ -556,6 +560,74 @@ bh_status bh_mpc_common_contribute(bh_ctx* ctx, const bh_mpc_common* storage, co
                                    const uint64_t beta[4], const uint64_t tau[4], bh_mpc_common_contrib** out);
 bh_status bh_mpc_common_verify(bh_ctx* ctx, const bh_mpc_common* storage, const bh_mpc_common_contrib* contrib,
                                const uint64_t* z, int* valid, bh_mpc_common** next);
+/* ---- the structure check of a round-one storage (no counterpart in the reference; DESIGN.md
+ * section 16).  bh_mpc_common_verify ties a contribution's alpha_mul_tau and beta_mul_tau lists to
+ * the storage element by element and never looks at the tau lists, and bh_mpc_common_matrix
+ * transforms whatever it is given; neither shows that a storage is a power sequence.  A storage of
+ * length len is WELL FORMED iff scalars tau, alpha, beta exist with tau_g1[i] = tau^i G1,
+ * tau_g2[i] = tau^i G2, alpha_mul_tau_g1/g2[i] = alpha tau^i G1/G2, the same for beta, and
+ * alpha_g1/g2 = alpha G1/G2, beta_g1/g2 = beta G1/G2.  bh_mpc_common_initial is, and so is every
+ * storage reached from it through bh_mpc_common_contribute.
+ *   bh_mpc_common_check   rho: ONE canonical scalar the caller draws at random (rho >= r or zero:
+ *                         BH_ERR_INVALID_ARGUMENT); the weights are w_i = rho^i, written on the
+ *                         device.  With S(V) = sum_{i < len} w_i V_i, L = sum_{i < len-1} w_i tau_g1[i]
+ *                         and R = sum_{i < len-1} w_i tau_g1[i+1], bit k of *failed (may be NULL) is
+ *                         set iff equation k fails, and *valid = (mask == 0):
+ *                           BH_MPC_CHECK_FIRST      tau_g1[0] == G1 and tau_g2[0] == G2 (bytes)
+ *                           BH_MPC_CHECK_ALPHA      e(alpha_g1, G2) == e(G1, alpha_g2)
+ *                           BH_MPC_CHECK_BETA       e(beta_g1, G2) == e(G1, beta_g2)
+ *                           BH_MPC_CHECK_POWERS     e(R, G2) == e(L, tau_g2[1])
+ *                           BH_MPC_CHECK_TAU_G2     e(S(tau_g1), G2) == e(G1, S(tau_g2))
+ *                           BH_MPC_CHECK_ALPHA_TAU  e(S(alpha_mul_tau_g1), G2) == e(S(tau_g1), alpha_g2)
+ *                           BH_MPC_CHECK_ALPHA_TAU_G2   ... == e(G1, S(alpha_mul_tau_g2))
+ *                           BH_MPC_CHECK_BETA_TAU, BH_MPC_CHECK_BETA_TAU_G2   the same two for beta
+ *                         Every equation is evaluated (no early exit); a sum that is the identity
+ *                         pairs to one.  FIRST is vacuous for len = 0 and POWERS for len < 2; len = 0
+ *                         evaluates ALPHA and BETA only.  A well-formed storage always passes; a
+ *                         malformed one passes an equation it violates with probability at most
+ *                         len / r over rho (below 2^-226 for len <= 2^28).  Cost: eight multiexps of
+ *                         length len (five in G1, three in G2) and nine pairing equations on the
+ *                         host's pool, whatever len is.
+ *   bh_mpc_common_verify_structure   verifies a contribution with O(1) pairings.  PRECONDITION:
+ *                         storage is well formed -- it is the initial one, or bh_mpc_common_check
+ *                         accepted it, or it came out of this function.  Accepts iff
+ *                           BH_MPC_CHECK_LENGTHS     all twelve vectors of contrib have storage's length
+ *                                                    (if not, this bit alone is set and nothing else runs)
+ *                           BH_MPC_CHECK_ALPHA_RATIO e(R1, G2) == e(O1, M2), the first equation of
+ *                                                    verify_new_paramter (mpc.rs:787-804), O1 = storage's
+ *                                                    alpha_g1, R1 = the result, M2 = the player's g2_mine
+ *                           BH_MPC_CHECK_BETA_RATIO  the same for beta
+ *                           BH_MPC_CHECK_TAU_RATIO   the same for element 1 of the tau pair: O1 = storage's
+ *                                                    tau_g1[1], R1 = the result's, M2 = mine tau_g2[1]
+ *                                                    (vacuous for len < 2)
+ *                           bits 0-8                 bh_mpc_common_check of contrib's to_storage_format()
+ *                         On acceptance *valid = 1 and *next is that storage, byte-identical under
+ *                         bh_mpc_common_write to what bh_mpc_common_verify returns; else 0 and NULL.
+ *                         It accepts everything bh_mpc_common_contribute makes from a well-formed
+ *                         storage and refuses tau lists bh_mpc_common_verify lets through.  The
+ *                         "mine" lists are NOT read beyond the three g2_mine above: the per-element
+ *                         proofs they carry are implied by the two storages being power sequences.
+ *   bh_mpc_last_check_ms  wall time (ms) of this thread's last check (either function): [0] the
+ *                         weights and the multiexps, [1] the pairings */
+#define BH_MPC_CHECK_FIRST (1u << 0)
+#define BH_MPC_CHECK_ALPHA (1u << 1)
+#define BH_MPC_CHECK_BETA (1u << 2)
+#define BH_MPC_CHECK_POWERS (1u << 3)
+#define BH_MPC_CHECK_TAU_G2 (1u << 4)
+#define BH_MPC_CHECK_ALPHA_TAU (1u << 5)
+#define BH_MPC_CHECK_ALPHA_TAU_G2 (1u << 6)
+#define BH_MPC_CHECK_BETA_TAU (1u << 7)
+#define BH_MPC_CHECK_BETA_TAU_G2 (1u << 8)
+#define BH_MPC_CHECK_LENGTHS (1u << 9)
+#define BH_MPC_CHECK_ALPHA_RATIO (1u << 10)
+#define BH_MPC_CHECK_BETA_RATIO (1u << 11)
+#define BH_MPC_CHECK_TAU_RATIO (1u << 12)
+bh_status bh_mpc_common_check(bh_ctx* ctx, const bh_mpc_common* storage, const uint64_t rho[4], int* valid,
+                              uint32_t* failed);
+bh_status bh_mpc_common_verify_structure(bh_ctx* ctx, const bh_mpc_common* storage,
+                                         const bh_mpc_common_contrib* contrib, const uint64_t rho[4], int* valid,
+                                         uint32_t* failed, bh_mpc_common** next);
+void bh_mpc_last_check_ms(double out[2]);
 bh_status bh_mpc_common_h_basis(bh_ctx* ctx, const bh_mpc_common* storage, size_t n, bh_srs** h_g1, bh_srs** h_g2);
 size_t bh_mpc_common_len(const bh_mpc_common* storage);
 bh_status bh_mpc_common_free(bh_mpc_common* storage);
@@ -616,6 +688,8 @@ bh_status bh_mpc_uncommon_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t
  *                          reference asserts it, mpc.rs:632).  BH_ERR_UNCONSTRAINED_VARIABLE: an aux
  *                          variable whose kout is the identity (generator.rs:586-590).
  *                          BH_ERR_UNEXPECTED_IDENTITY: an identity among kin or h, or from a transform.
+ *                          Beyond tau_g1[0] the vectors are taken as given: run bh_mpc_common_check
+ *                          on a storage of unknown origin first.
  *   bh_mpc_parameters      generator.rs:207-236 with the queries filled in: vk = alpha_g1, beta_g1,
  *                          beta_g2 of round one, gamma_g2, delta_g1, delta_g2 of round two, ic = round
  *                          two's kin_g1; l = kout_g1; h = the first m - 1 of h_g1; a, b_g1, b_g2 from
