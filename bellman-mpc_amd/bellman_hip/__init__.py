@@ -181,6 +181,8 @@ def _load():
         "bh_srs_sub_range": (I, [P, P, S, S, S, P]),
         "bh_srs_fft": (I, [P, P, I, P]),
         "bh_srs_read": (I, [P, S, S, P]),
+        "bh_srs_upload_compressed": (I, [P, I, P, S, I, P]),
+        "bh_srs_read_compressed": (I, [P, S, S, P]),
         "bh_mpc_common_matrix": (I, [P, P, P, P]),
         "bh_mpc_matrix_vector": (I, [P, I, P]),
         "bh_mpc_matrix_free": (I, [P]),
@@ -213,6 +215,8 @@ def _load():
             sig[f"bh_mpc_{kind}{who}_point"] = (I, [P, I, P])
             sig[f"bh_mpc_{kind}{who}_write"] = (I, [P, P, S, P])
             sig[f"bh_mpc_{kind}{who}_read"] = (I, [P, P, S, I, P])
+            sig[f"bh_mpc_{kind}{who}_write_compressed"] = (I, [P, P, S, P])
+            sig[f"bh_mpc_{kind}{who}_read_compressed"] = (I, [P, P, S, I, P])
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
         f.restype = res
@@ -250,8 +254,9 @@ EXPORTED_SYMBOLS = [
     "bh_srs_fft", "bh_srs_read", "bh_mpc_common_matrix", "bh_mpc_matrix_vector", "bh_mpc_matrix_free",
     "bh_mpc_parameters", "bh_mpc_last_matrix_ms", "bh_final_exponentiation_batch", "bh_verify_each_device",
     "bh_mpc_common_check", "bh_mpc_common_verify_structure", "bh_mpc_last_check_ms",
+    "bh_srs_upload_compressed", "bh_srs_read_compressed",
 ] + [f"bh_mpc_{kind}{who}_{op}" for kind in ("common", "uncommon") for who in ("", "_contrib")
-     for op in ("free", "vector", "point", "write", "read")]
+     for op in ("free", "vector", "point", "write", "read", "write_compressed", "read_compressed")]
 BH_VEC_H, BH_VEC_L, BH_VEC_A, BH_VEC_B_G1, BH_VEC_B_G2 = range(5)
 PARTIAL_BYTES = 960
 
@@ -420,6 +425,20 @@ class Bases:
         return _lib.bh_srs_len(self.h)
 
     @classmethod
+    def from_compressed(cls, ctx, group, data: bytes, checked=True):
+        """The vector of len(data) / 48 (96) compressed points, decoded on the device
+        (bh_srs_upload_compressed).  Flags, range and squareness are always checked; checked adds the
+        subgroup test."""
+        pb = 48 if group == BH_G1 else 96
+        assert len(data) % pb == 0
+        n = len(data) // pb
+        buf = np.frombuffer(data, dtype=np.uint8) if n else np.zeros(1, np.uint8)
+        h = ctypes.c_void_p()
+        _check(_lib.bh_srs_upload_compressed(ctx.h, group, _ptr(buf), n, int(checked), ctypes.byref(h)),
+               "bh_srs_upload_compressed")
+        return cls._adopt(ctx, group, h)
+
+    @classmethod
     def _adopt(cls, ctx, group, handle):
         """A bh_srs the library returned (owned: freed with the object)."""
         b = cls.__new__(cls)
@@ -469,11 +488,20 @@ class Bases:
         """The inverse transform (omega^-1, then 1/n): of tau^i G, the Lagrange basis L_i(tau) G."""
         return self.fft(inverse=True)
 
-    def read(self, first, n):
-        """Bases first .. first + n as uncompressed bytes, in one copy."""
-        out = np.zeros(max(n, 1) * (96 if self.group == BH_G1 else 192), dtype=np.uint8)
-        _check(_lib.bh_srs_read(self.h, first, n, _ptr(out)), "bh_srs_read")
-        return out[:n * (96 if self.group == BH_G1 else 192)].tobytes()
+    def read(self, first, n, compressed=False):
+        """Bases first .. first + n as uncompressed bytes, in one copy; compressed: as compressed
+        bytes, encoded on the device (bh_srs_read_compressed)."""
+        pb = (96 if self.group == BH_G1 else 192) // (2 if compressed else 1)
+        out = np.zeros(max(n, 1) * pb, dtype=np.uint8)
+        if compressed:
+            _check(_lib.bh_srs_read_compressed(self.h, first, n, _ptr(out)), "bh_srs_read_compressed")
+        else:
+            _check(_lib.bh_srs_read(self.h, first, n, _ptr(out)), "bh_srs_read")
+        return out[:n * pb].tobytes()
+
+    def to_compressed(self):
+        """The whole vector as compressed bytes (48 B per G1 point, 96 B per G2 point)."""
+        return self.read(0, len(self), compressed=True)
 
     def to_bytes(self):
         return b"".join(self.get(i) for i in range(len(self)))
@@ -1685,19 +1713,21 @@ class _MpcHandle:
     def _fn(self, op):
         return getattr(_lib, f"bh_mpc_{self._KIND}_{op}")
 
-    def write(self):
+    def write(self, compressed=False):
+        """The handle's bytes; compressed: the same layout with every point compressed."""
+        fn = self._fn("write_compressed" if compressed else "write")
         n = ctypes.c_size_t()
-        _check(self._fn("write")(self.h, None, 0, ctypes.byref(n)))
+        _check(fn(self.h, None, 0, ctypes.byref(n)))
         out = np.zeros(max(n.value, 1), dtype=np.uint8)
-        _check(self._fn("write")(self.h, _ptr(out), n.value, ctypes.byref(n)))
+        _check(fn(self.h, _ptr(out), n.value, ctypes.byref(n)))
         return out[:n.value].tobytes()
 
     @classmethod
-    def read(cls, ctx, data: bytes, checked=True):
+    def read(cls, ctx, data: bytes, checked=True, compressed=False):
         buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
         h = ctypes.c_void_p()
-        _check(getattr(_lib, f"bh_mpc_{cls._KIND}_read")(ctx.h, _ptr(buf), len(data), int(checked), ctypes.byref(h)),
-               f"{cls.__name__}::read")
+        fn = getattr(_lib, f"bh_mpc_{cls._KIND}_read" + ("_compressed" if compressed else ""))
+        _check(fn(ctx.h, _ptr(buf), len(data), int(checked), ctypes.byref(h)), f"{cls.__name__}::read")
         return cls(ctx, h)
 
     def point(self, which):

@@ -123,6 +123,17 @@ __global__ void __launch_bounds__(256) k_subgroup_check(const uint32_t* pts, siz
   if (!C::is_identity(acc)) atomicOr(bad, 2u);
 }
 
+// k_subgroup_check over n device-form points for callers outside this unit (point_codec.hip):
+// enqueued on ctx->stream; *d_bad (a zeroed device word) becomes non-zero when a point is outside
+bh_status subgroup_check_enqueue(bh_ctx* ctx, int group, const uint32_t* pts, size_t n, uint32_t* d_bad) {
+  if (!n) return BH_OK;
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  if (group == BH_G1) hipLaunchKernelGGL(k_subgroup_check<G1Ops>, dim3(blocks), dim3(256), 0, ctx->stream, pts, n, d_bad);
+  else hipLaunchKernelGGL(k_subgroup_check<G2Ops>, dim3(blocks), dim3(256), 0, ctx->stream, pts, n, d_bad);
+  BH_TRY_HIP(hipGetLastError());
+  return BH_OK;
+}
+
 // ------------------------------------------------------------------ SRS
 // canonical packed words of out->n points -> out->pts in device form; checked: every point is on
 // the curve and in the subgroup

@@ -510,6 +510,10 @@ bh_status run_h_vector(bh_ctx* ctx, Domain* D, uint32_t* d_abc, hipStream_t st, 
 bh_status run_h_final(bh_ctx* ctx, Domain* D, uint32_t* d_abc, hipStream_t st, uint32_t* hout);
 bh_status srs_from_bytes(bh_ctx* ctx, int group, const uint8_t* bytes, size_t n, int checked, bool reject_identity,
                          bh_srs* out);
+// api.hip's k_subgroup_check over n device-form points (all-zero records, the identity, are
+// skipped), enqueued on ctx->stream: the zeroed device word *d_bad becomes non-zero when a point is
+// outside the subgroup
+bh_status subgroup_check_enqueue(bh_ctx* ctx, int group, const uint32_t* pts, size_t n, uint32_t* d_bad);
 // reference-exact error semantics of multiexp (EOF / identity), host side
 bh_status multiexp_check(const bh_srs* bases, size_t base_offset, const uint64_t* density_words, size_t n,
                          const uint64_t* exps_canonical, bool need_exps);

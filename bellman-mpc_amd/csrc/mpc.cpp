@@ -25,6 +25,7 @@
 #include "group_fft.h"
 #include "pairing.h"
 #include "pairing_dev.h"
+#include "point_codec.h"
 #include "r1cs.h"
 #include "varbase.h"
 
@@ -254,17 +255,29 @@ void put_u32(std::vector<uint8_t>& v, size_t n) {
   v.push_back((uint8_t)(n >> 8));
   v.push_back((uint8_t)n);
 }
-template <class T>
-void put(std::vector<uint8_t>& v, const AffinePt<T>& p) {
-  uint8_t b[HostOfField<T>::WIRE];
-  to_uncompressed(p, b);
-  v.insert(v.end(), b, b + sizeof b);
+// Every writer and reader below takes one `compressed` switch: the layouts are the same, each
+// point 48 / 96 bytes instead of 96 / 192.  Single points go through the host's to_compressed /
+// point_from_compressed, vectors through the device codec (point_codec.hip).
+size_t wire_bytes(int group, bool compressed) {
+  return compressed ? compressed_bytes(group) : with_group(group, [](auto g) { return decltype(g)::WIRE; });
 }
-bh_status put_vec(std::vector<uint8_t>& v, const bh_srs* s) {
+template <class T>
+void put(std::vector<uint8_t>& v, const AffinePt<T>& p, bool compressed) {
+  uint8_t b[HostOfField<T>::WIRE];
+  if (compressed) to_compressed(p, b);
+  else to_uncompressed(p, b);
+  v.insert(v.end(), b, b + wire_bytes(HostOfField<T>::ID, compressed));
+}
+bh_status put_vec(std::vector<uint8_t>& v, bh_ctx* ctx, const bh_srs* s, bool compressed) {
+  if (compressed) {
+    const size_t at = v.size();
+    v.resize(at + s->n * compressed_bytes(s->group));
+    return srs_to_compressed(ctx, s, 0, s->n, v.data() + at);
+  }
   return with_group(s->group, [&](auto g) {
     std::vector<typename decltype(g)::Affine> h;
     const bh_status st = download(s, &h);
-    for (const auto& p : h) put(v, p);
+    for (const auto& p : h) put(v, p, false);
     return st;
   });
 }
@@ -273,6 +286,7 @@ struct Reader {
   const uint8_t* in;
   size_t len, o = 0;
   int checked;
+  bool compressed;
   bh_status u32(size_t* n) {
     if (len - o < 4) return BH_ERR_UNEXPECTED_EOF;
     *n = ((size_t)in[o] << 24) | ((size_t)in[o + 1] << 16) | ((size_t)in[o + 2] << 8) | in[o + 3];
@@ -281,44 +295,85 @@ struct Reader {
   }
   template <class T>
   bh_status point(AffinePt<T>* p) {
-    constexpr size_t pb = HostOfField<T>::WIRE;
+    const size_t pb = wire_bytes(HostOfField<T>::ID, compressed);
     if (len - o < pb) return BH_ERR_UNEXPECTED_EOF;
-    const int r = from_uncompressed(in + o, p, checked != 0, checked != 0);
     o += pb;
+    if (compressed) return point_from_compressed(in + o - pb, p, checked != 0);  // refuses the identity
+    const int r = from_uncompressed(in + o - pb, p, checked != 0, checked != 0);
     if (r == -3) return BH_ERR_NOT_IN_SUBGROUP;
     if (r == -2) return BH_ERR_NOT_ON_CURVE;
     return (r || p->infinity) ? BH_ERR_INVALID_ENCODING : BH_OK;
   }
   // n consecutive points of one group -> device vector (the checks of bh_params_load)
   bh_status vec(bh_ctx* ctx, int group, size_t n, std::unique_ptr<bh_srs>* out) {
-    const size_t pb = with_group(group, [](auto g) { return decltype(g)::WIRE; });
+    const size_t pb = wire_bytes(group, compressed);
     if (n > (len - o) / pb) return BH_ERR_UNEXPECTED_EOF;
     out->reset(new bh_srs());
-    const bh_status s = srs_from_bytes(ctx, group, in + o, n, checked, true, out->get());
+    const bh_status s = compressed ? srs_from_compressed(ctx, group, in + o, n, checked, true, out->get())
+                                   : srs_from_bytes(ctx, group, in + o, n, checked, true, out->get());
     o += n * pb;
     return s;
+  }
+  // n ParameterPairs (g1_result, g2_result, g1_mine, g2_mine per element) -> their four vectors
+  bh_status pairs(bh_ctx* ctx, size_t n, std::unique_ptr<bh_srs>* const dst[4]) {
+    size_t w[4], pair = 0;
+    for (int k = 0; k < 4; k++) pair += w[k] = wire_bytes(k & 1 ? BH_G2 : BH_G1, compressed);
+    if (n > (len - o) / pair) return BH_ERR_UNEXPECTED_EOF;
+    const uint8_t* list = in + o;
+    o += n * pair;
+    for (int k = 0; k < 4; k++) dst[k]->reset(new bh_srs());
+    bh_status s;
+    if (compressed) {  // the interleaved list goes to the device as it is; the codec reads it strided
+      DevBuf raw;
+      BH_TRY_HIP(raw.alloc(std::max<size_t>(n * pair, 16)));
+      if (n) BH_TRY_HIP(hipMemcpyAsync(raw.p, list, n * pair, hipMemcpyHostToDevice, ctx->stream));
+      size_t off = 0;
+      for (int k = 0; k < 4; k++) {
+        // each call returns synchronised, so raw outlives every read of it
+        if ((s = points_decompress_device(ctx, k & 1 ? BH_G2 : BH_G1, raw.as<uint8_t>(), pair, off, n, checked, true,
+                                          dst[k]->get())))
+          return s;
+        off += w[k];
+      }
+      return BH_OK;
+    }
+    // de-interleave the list into its four vectors
+    std::vector<uint8_t> col[4];
+    for (int k = 0; k < 4; k++) col[k].resize(n * w[k]);
+    for (size_t i = 0; i < n; i++) {
+      const uint8_t* b = list + i * pair;
+      size_t off = 0;
+      for (int k = 0; k < 4; k++) {
+        memcpy(&col[k][i * w[k]], b + off, w[k]);
+        off += w[k];
+      }
+    }
+    for (int k = 0; k < 4; k++)
+      if ((s = srs_from_bytes(ctx, k & 1 ? BH_G2 : BH_G1, col[k].data(), n, checked, true, dst[k]->get()))) return s;
+    return BH_OK;
   }
 };
 
 // storage bytes.  common: u32-BE len, the four points, the six vectors; uncommon (vector pairs
 // of different lengths): the four points, then every vector behind its own u32-BE length
-bh_status storage_write(const MpcStorage* st, bool common, std::vector<uint8_t>& v) {
+bh_status storage_write(const MpcStorage* st, bool common, bool compressed, std::vector<uint8_t>& v) {
   if (common) put_u32(v, st->v[0]->n);
   for (int k = 0; k < 2; k++) {
-    put(v, st->p1[k]);
-    put(v, st->p2[k]);
+    put(v, st->p1[k], compressed);
+    put(v, st->p2[k], compressed);
   }
   for (int k = 0; k < 6; k++) {
     if (!common) put_u32(v, st->v[k]->n);
-    bh_status s = put_vec(v, st->v[k].get());
+    bh_status s = put_vec(v, st->ctx, st->v[k].get(), compressed);
     if (s) return s;
   }
   return BH_OK;
 }
 
 template <class S>
-bh_status storage_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bool common, S** out) {
-  Reader r{bytes, len, 0, checked};
+bh_status storage_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bool common, bool compressed,
+                       S** out) {
+  Reader r{bytes, len, 0, checked, compressed};
   std::unique_ptr<S> st(new S());
   st->ctx = ctx;
   bh_status s;
@@ -347,15 +402,40 @@ bh_status storage_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checke
 // contribution bytes: the ParameterPairs in declaration order (common: alpha, beta; uncommon:
 // delta, gamma), each g1_result, g2_result, g1_mine, g2_mine; then the three TauParameterPairs,
 // each a u32-BE length and that many ParameterPairs
-bh_status contrib_write(const MpcContrib* c, bool common, std::vector<uint8_t>& v) {
+bh_status contrib_write(const MpcContrib* c, bool common, bool compressed, std::vector<uint8_t>& v) {
   for (int k = 0; k < 2; k++) {
     const HostPair& p = c->pp[common ? k : 1 - k];
-    put(v, p.r1);
-    put(v, p.r2);
-    put(v, p.m1);
-    put(v, p.m2);
+    put(v, p.r1, compressed);
+    put(v, p.r2, compressed);
+    put(v, p.m1, compressed);
+    put(v, p.m2, compressed);
   }
   for (int j = 0; j < 3; j++) {
+    if (compressed) {  // the four vectors coded into one interleaved device list, one copy back
+      const bh_srs* col[4] = {c->res[2 * j].get(), c->res[2 * j + 1].get(), c->mine[2 * j].get(),
+                              c->mine[2 * j + 1].get()};
+      const size_t n = col[0]->n, pair = 2 * (compressed_bytes(BH_G1) + compressed_bytes(BH_G2));
+      put_u32(v, n);
+      const size_t at = v.size();
+      v.resize(at + n * pair);
+      if (!n) continue;
+      DevBuf d;
+      BH_TRY_HIP(d.alloc(n * pair));
+      size_t off = 0;
+      for (int k = 0; k < 4; k++) {
+        if (col[k]->n != n) return BH_ERR_INVALID_ARGUMENT;
+        if (bh_status s = points_compress_device(c->ctx, col[k], 0, n, d.as<uint8_t>(), pair, off)) return s;
+        off += compressed_bytes(col[k]->group);
+      }
+      BH_TRY_HIP(hipMemcpyAsync(v.data() + at, d.p, n * pair, hipMemcpyDeviceToHost, c->ctx->stream));
+      BH_TRY_HIP(hipStreamSynchronize(c->ctx->stream));  // d is freed at the end of the round
+      off = 0;
+      for (int k = 0; k < 4; k++) {
+        points_compress_patch(col[k], 0, n, v.data() + at, pair, off);
+        off += compressed_bytes(col[k]->group);
+      }
+      continue;
+    }
     std::vector<AffinePt<Fp>> r1, m1;
     std::vector<AffinePt<Fp2>> r2, m2;
     bh_status s;
@@ -364,18 +444,19 @@ bh_status contrib_write(const MpcContrib* c, bool common, std::vector<uint8_t>& 
       return s;
     put_u32(v, r1.size());
     for (size_t i = 0; i < r1.size(); i++) {
-      put(v, r1[i]);
-      put(v, r2[i]);
-      put(v, m1[i]);
-      put(v, m2[i]);
+      put(v, r1[i], false);
+      put(v, r2[i], false);
+      put(v, m1[i], false);
+      put(v, m2[i], false);
     }
   }
   return BH_OK;
 }
 
 template <class Cn>
-bh_status contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bool common, Cn** out) {
-  Reader r{bytes, len, 0, checked};
+bh_status contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bool common, bool compressed,
+                       Cn** out) {
+  Reader r{bytes, len, 0, checked, compressed};
   std::unique_ptr<Cn> c(new Cn());
   c->ctx = ctx;
   bh_status s;
@@ -386,26 +467,8 @@ bh_status contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checke
   for (int j = 0; j < 3; j++) {
     size_t n;
     if ((s = r.u32(&n))) return s;
-    const size_t w[4] = {G1Host::WIRE, G2Host::WIRE, G1Host::WIRE, G2Host::WIRE};
-    const size_t pair = w[0] + w[1] + w[2] + w[3];
-    if (n > (len - r.o) / pair) return BH_ERR_UNEXPECTED_EOF;
-    // de-interleave the list into its four vectors
-    std::vector<uint8_t> col[4];
-    for (int k = 0; k < 4; k++) col[k].resize(n * w[k]);
-    for (size_t i = 0; i < n; i++) {
-      const uint8_t* b = bytes + r.o + i * pair;
-      size_t off = 0;
-      for (int k = 0; k < 4; k++) {
-        memcpy(&col[k][i * w[k]], b + off, w[k]);
-        off += w[k];
-      }
-    }
-    r.o += n * pair;
-    std::unique_ptr<bh_srs>* dst[4] = {&c->res[2 * j], &c->res[2 * j + 1], &c->mine[2 * j], &c->mine[2 * j + 1]};
-    for (int k = 0; k < 4; k++) {
-      dst[k]->reset(new bh_srs());
-      if ((s = srs_from_bytes(ctx, k & 1 ? BH_G2 : BH_G1, col[k].data(), n, checked, true, dst[k]->get()))) return s;
-    }
+    std::unique_ptr<bh_srs>* const dst[4] = {&c->res[2 * j], &c->res[2 * j + 1], &c->mine[2 * j], &c->mine[2 * j + 1]};
+    if ((s = r.pairs(ctx, n, dst))) return s;
   }
   if (r.o != len) return BH_ERR_INVALID_ENCODING;
   *out = c.release();
@@ -461,6 +524,42 @@ struct CtxLock {
   CtxLock _lock(ctx);                       \
   BH_TRY_HIP(hipSetDevice((ctx)->device)); \
   if (bh_status _s = scratch_check(ctx)) return _s
+
+// the entry points' shared halves: a handle's bytes under its context's lock, and the checks in
+// front of a read
+template <class H, class Write>
+bh_status handle_bytes(const H* h, Write&& write, uint8_t* out, size_t cap, size_t* written) {
+  if (!h || !written) return BH_ERR_INVALID_ARGUMENT;
+  std::vector<uint8_t> v;
+  {
+    CtxLock lk(h->ctx);
+    BH_TRY_HIP(hipSetDevice(h->ctx->device));
+    if (bh_status s = write(v)) return s;
+  }
+  return emit(v, out, cap, written);
+}
+bh_status storage_bytes(const MpcStorage* st, bool common, bool compressed, uint8_t* out, size_t cap, size_t* written) {
+  return handle_bytes(st, [&](std::vector<uint8_t>& v) { return storage_write(st, common, compressed, v); }, out, cap,
+                      written);
+}
+bh_status contrib_bytes(const MpcContrib* c, bool common, bool compressed, uint8_t* out, size_t cap, size_t* written) {
+  return handle_bytes(c, [&](std::vector<uint8_t>& v) { return contrib_write(c, common, compressed, v); }, out, cap,
+                      written);
+}
+template <class S>
+bh_status storage_parse(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bool common, bool compressed,
+                        S** out) {
+  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  return storage_read(ctx, bytes, len, checked, common, compressed, out);
+}
+template <class Cn>
+bh_status contrib_parse(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bool common, bool compressed,
+                        Cn** out) {
+  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
+  MPC_ENTER(ctx);
+  return contrib_read(ctx, bytes, len, checked, common, compressed, out);
+}
 
 thread_local double g_miller_ms = 0;
 thread_local int g_miller_device = 0;
@@ -739,35 +838,32 @@ bh_status bh_mpc_common_contrib_point(const bh_mpc_common_contrib* c, int which,
 }
 
 bh_status bh_mpc_common_write(const bh_mpc_common* st, uint8_t* out, size_t cap, size_t* written) {
-  if (!st || !written) return BH_ERR_INVALID_ARGUMENT;
-  std::vector<uint8_t> v;
-  {
-    CtxLock lk(st->ctx);
-    BH_TRY_HIP(hipSetDevice(st->ctx->device));
-    if (bh_status s = storage_write(st, true, v)) return s;
-  }
-  return emit(v, out, cap, written);
+  return storage_bytes(st, true, false, out, cap, written);
+}
+bh_status bh_mpc_common_write_compressed(const bh_mpc_common* st, uint8_t* out, size_t cap, size_t* written) {
+  return storage_bytes(st, true, true, out, cap, written);
 }
 bh_status bh_mpc_common_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_mpc_common** out) {
-  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
-  MPC_ENTER(ctx);
-  return storage_read(ctx, bytes, len, checked, true, out);
+  return storage_parse(ctx, bytes, len, checked, true, false, out);
+}
+bh_status bh_mpc_common_read_compressed(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                        bh_mpc_common** out) {
+  return storage_parse(ctx, bytes, len, checked, true, true, out);
 }
 bh_status bh_mpc_common_contrib_write(const bh_mpc_common_contrib* c, uint8_t* out, size_t cap, size_t* written) {
-  if (!c || !written) return BH_ERR_INVALID_ARGUMENT;
-  std::vector<uint8_t> v;
-  {
-    CtxLock lk(c->ctx);
-    BH_TRY_HIP(hipSetDevice(c->ctx->device));
-    if (bh_status s = contrib_write(c, true, v)) return s;
-  }
-  return emit(v, out, cap, written);
+  return contrib_bytes(c, true, false, out, cap, written);
+}
+bh_status bh_mpc_common_contrib_write_compressed(const bh_mpc_common_contrib* c, uint8_t* out, size_t cap,
+                                                 size_t* written) {
+  return contrib_bytes(c, true, true, out, cap, written);
 }
 bh_status bh_mpc_common_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
                                      bh_mpc_common_contrib** out) {
-  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
-  MPC_ENTER(ctx);
-  return contrib_read(ctx, bytes, len, checked, true, out);
+  return contrib_parse(ctx, bytes, len, checked, true, false, out);
+}
+bh_status bh_mpc_common_contrib_read_compressed(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                                bh_mpc_common_contrib** out) {
+  return contrib_parse(ctx, bytes, len, checked, true, true, out);
 }
 
 // ================================================================ round two
@@ -871,35 +967,32 @@ bh_status bh_mpc_uncommon_contrib_point(const bh_mpc_uncommon_contrib* c, int wh
   return contrib_point(c, which, out);
 }
 bh_status bh_mpc_uncommon_write(const bh_mpc_uncommon* st, uint8_t* out, size_t cap, size_t* written) {
-  if (!st || !written) return BH_ERR_INVALID_ARGUMENT;
-  std::vector<uint8_t> v;
-  {
-    CtxLock lk(st->ctx);
-    BH_TRY_HIP(hipSetDevice(st->ctx->device));
-    if (bh_status s = storage_write(st, false, v)) return s;
-  }
-  return emit(v, out, cap, written);
+  return storage_bytes(st, false, false, out, cap, written);
+}
+bh_status bh_mpc_uncommon_write_compressed(const bh_mpc_uncommon* st, uint8_t* out, size_t cap, size_t* written) {
+  return storage_bytes(st, false, true, out, cap, written);
 }
 bh_status bh_mpc_uncommon_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_mpc_uncommon** out) {
-  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
-  MPC_ENTER(ctx);
-  return storage_read(ctx, bytes, len, checked, false, out);
+  return storage_parse(ctx, bytes, len, checked, false, false, out);
+}
+bh_status bh_mpc_uncommon_read_compressed(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                          bh_mpc_uncommon** out) {
+  return storage_parse(ctx, bytes, len, checked, false, true, out);
 }
 bh_status bh_mpc_uncommon_contrib_write(const bh_mpc_uncommon_contrib* c, uint8_t* out, size_t cap, size_t* written) {
-  if (!c || !written) return BH_ERR_INVALID_ARGUMENT;
-  std::vector<uint8_t> v;
-  {
-    CtxLock lk(c->ctx);
-    BH_TRY_HIP(hipSetDevice(c->ctx->device));
-    if (bh_status s = contrib_write(c, false, v)) return s;
-  }
-  return emit(v, out, cap, written);
+  return contrib_bytes(c, false, false, out, cap, written);
+}
+bh_status bh_mpc_uncommon_contrib_write_compressed(const bh_mpc_uncommon_contrib* c, uint8_t* out, size_t cap,
+                                                   size_t* written) {
+  return contrib_bytes(c, false, true, out, cap, written);
 }
 bh_status bh_mpc_uncommon_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
                                        bh_mpc_uncommon_contrib** out) {
-  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
-  MPC_ENTER(ctx);
-  return contrib_read(ctx, bytes, len, checked, false, out);
+  return contrib_parse(ctx, bytes, len, checked, false, false, out);
+}
+bh_status bh_mpc_uncommon_contrib_read_compressed(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                                  bh_mpc_uncommon_contrib** out) {
+  return contrib_parse(ctx, bytes, len, checked, false, true, out);
 }
 
 // ================================================================ between the rounds

@@ -3,6 +3,7 @@
 #pragma once
 #include <vector>
 
+#include "../../include/bellman_hip.h"
 #include "host_arith.h"
 
 namespace bh {
@@ -24,5 +25,12 @@ Fp12 multi_miller_loop(const std::vector<Pair>& pairs);
 Fp12 final_exponentiation(const Fp12& f);
 // prod_i e(p_i, q_i) == 1
 bool pairing_product_is_one(const std::vector<Pair>& pairs);
+
+// G1Affine / G2Affine::from_compressed_unchecked of one point (48 / 96 bytes), the identity refused
+// as Proof::read refuses it; check_subgroup adds the torsion test of from_compressed.
+// BH_ERR_INVALID_ENCODING: the compression flag clear, the infinity flag set, a coordinate >= p or
+// x^3 + b not a square, in that order; BH_ERR_NOT_IN_SUBGROUP.
+template <class T>
+bh_status point_from_compressed(const uint8_t* in, AffinePt<T>* out, bool check_subgroup);
 
 }  // namespace bh

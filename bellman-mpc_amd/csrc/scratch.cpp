@@ -21,6 +21,7 @@
 #include "dist_h.h"
 #include "group_fft.h"
 #include "pairing_dev.h"
+#include "point_codec.h"
 #include "proofs_dev.h"
 #include "r1cs.h"
 #include "varbase.h"
@@ -95,6 +96,7 @@ bh_status scratch_report(bh_ctx* ctx, uint64_t out[10], std::string* worst) {
   group_fft_kernels(ks);
   pairing_kernels(ks);
   proofs_kernels(ks);
+  point_codec_kernels(ks);
   verify_each_kernels(ks);
   const uint64_t cus = (uint64_t)std::max(prop.multiProcessorCount, 1);
   const uint64_t slots_per_cu = 32;  // KFD max_slots_scratch_cu (profiles/r03_kfd_queue_props.txt)

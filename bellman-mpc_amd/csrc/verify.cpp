@@ -211,9 +211,14 @@ bool field_sqrt(const Fp2& a, Fp2* out) {  // p = 3 mod 4 algorithm over Fp2 = F
   return true;
 }
 
-// G1Affine / G2Affine::from_compressed + Proof::read's identity rejection
+}  // namespace
+
+namespace bh {
+
+// pairing.h: the decoder of one compressed point (the order of its checks is the one the device
+// decoders follow)
 template <class T>
-bh_status from_compressed(const uint8_t* in, AffinePt<T>* out) {
+bh_status point_from_compressed(const uint8_t* in, AffinePt<T>* out, bool check_subgroup) {
   const uint8_t flags = in[0] >> 5;
   if (!(flags & 0x4)) return BH_ERR_INVALID_ENCODING;  // compression flag
   if (flags & 0x2) return BH_ERR_INVALID_ENCODING;     // the identity ("point at infinity")
@@ -223,8 +228,20 @@ bh_status from_compressed(const uint8_t* in, AffinePt<T>* out) {
   if (!field_sqrt(add(mul(sqr(out->x), out->x), CurveB<T>::b()), &out->y)) return BH_ERR_INVALID_ENCODING;
   if (lex_largest(out->y) != ((flags & 0x1) != 0)) out->y = neg(out->y);
   out->infinity = false;
-  if (!in_subgroup(*out)) return BH_ERR_NOT_IN_SUBGROUP;
+  if (check_subgroup && !in_subgroup(*out)) return BH_ERR_NOT_IN_SUBGROUP;
   return BH_OK;
+}
+template bh_status point_from_compressed<Fp>(const uint8_t*, AffinePt<Fp>*, bool);
+template bh_status point_from_compressed<Fp2>(const uint8_t*, AffinePt<Fp2>*, bool);
+
+}  // namespace bh
+
+namespace {
+
+// G1Affine / G2Affine::from_compressed + Proof::read's identity rejection
+template <class T>
+bh_status from_compressed(const uint8_t* in, AffinePt<T>* out) {
+  return bh::point_from_compressed(in, out, true);
 }
 
 struct Proof {

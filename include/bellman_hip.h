@@ -121,6 +121,27 @@ size_t bh_srs_len(const bh_srs* srs);
 bh_status bh_srs_get(const bh_srs* srs, size_t i, uint8_t* out);
 /* the same for bases first .. first + n in one copy: out receives n * 96 (192) bytes */
 bh_status bh_srs_read(const bh_srs* srs, size_t first, size_t n, uint8_t* out);
+/* The compressed half of the encodings (48 B G1: x; 96 B G2: x.c1 then x.c0; the compression flag,
+ * the infinity flag and the sort flag = lex_largest(y) in the top bits of byte 0), coded on the
+ * device one lane per point.
+ *   bh_srs_upload_compressed  n compressed points -> a bh_srs that is word for word the one
+ *                             bh_srs_upload builds from the same points' uncompressed bytes.  A
+ *                             compressed point does not exist until it is decoded, so the flags, the
+ *                             range of every coordinate and the squareness of x^3 + b are ALWAYS
+ *                             checked, whatever `checked` is: any failing point gives
+ *                             BH_ERR_INVALID_ENCODING (the compression flag clear; an infinity flag
+ *                             with the sort flag or any other bit set; a coordinate >= p -- G2: c1
+ *                             under the flags, and c0; x^3 + b not a square).  checked adds the
+ *                             subgroup test only: BH_ERR_NOT_IN_SUBGROUP when every point decodes and
+ *                             one is outside.  BH_ERR_NOT_ON_CURVE cannot arise.  The valid infinity
+ *                             encoding (c0 00 ... 00) is accepted as bh_srs_upload accepts the
+ *                             uncompressed one.  n = 0 gives an empty vector; argument errors as
+ *                             bh_srs_upload.
+ *   bh_srs_read_compressed    bases first .. first + n as compressed bytes: out receives n * 48 (96)
+ *                             bytes; argument errors as bh_srs_read. */
+bh_status bh_srs_upload_compressed(bh_ctx* ctx, int group, const uint8_t* compressed_be, size_t n, int checked,
+                                   bh_srs** out);
+bh_status bh_srs_read_compressed(const bh_srs* srs, size_t first, size_t n, uint8_t* out);
 
 /* ---- multiexp::multiexp.  density_words == NULL means FullDensity.  out: uncompressed
  * encoding of the projective result normalised to affine (96 B for G1, 192 B for G2). */
@@ -522,6 +543,17 @@ bh_status bh_srs_fft(bh_ctx* ctx, const bh_srs* in, int inverse, bh_srs** out);
  *                             then each TauParameterPair as u32-BE len and its ParameterPairs.  out ==
  *                             NULL queries the size.  checked: the on-curve and subgroup checks of
  *                             bh_params_load; the identity is refused either way.
+ *   bh_mpc_common_write_compressed / _read_compressed, bh_mpc_common_contrib_write_compressed /
+ *   _read_compressed:         the same layouts with every point compressed (48 B G1, 96 B G2), the
+ *                             form to ship: a storage is 4 + 288 + 432 len bytes, a contribution
+ *                             576 + 3 (4 + 288 len).  Arguments as the uncompressed functions.  The
+ *                             vectors are coded on the device (bh_srs_upload_compressed's rules), the
+ *                             handful of single points on the host.  Reading always checks flags,
+ *                             range and squareness (BH_ERR_INVALID_ENCODING); checked adds the subgroup
+ *                             test (BH_ERR_NOT_IN_SUBGROUP).  The identity is refused
+ *                             (BH_ERR_INVALID_ENCODING); short input: BH_ERR_UNEXPECTED_EOF; trailing
+ *                             bytes: BH_ERR_INVALID_ENCODING.  read_compressed then write gives the
+ *                             bytes write gave before write_compressed.
  * Round two, "uncommon" parameters (mpc.rs:891-1131): UnCommonParamterInStorage (gamma_g1/g2,
  * delta_g1/g2, kin, kout, h) and UnCommonParamter (delta, gamma, ic, l, h).
  *   bh_mpc_uncommon_initial     initial_uncommon_paramters (mpc.rs:993-1015) from the six vectors of
@@ -534,7 +566,10 @@ bh_status bh_srs_fft(bh_ctx* ctx, const bh_srs* in, int inverse, bh_srs** out);
  *                               a G2 element on each side and collapse to
  *                               e(sum z_i new_i, gamma_or_delta_g2) == e(sum z_i matrix_i, G2).
  *   bytes: the four points, then each vector behind its own u32-BE length; the contribution as in
- *   round one with the ParameterPairs in the order delta, gamma. */
+ *   round one with the ParameterPairs in the order delta, gamma.  bh_mpc_uncommon_write_compressed /
+ *   _read_compressed and bh_mpc_uncommon_contrib_write_compressed / _read_compressed: the same with
+ *   every point compressed, as in round one; a pair's vectors of different lengths:
+ *   BH_ERR_INVALID_ENCODING. */
 typedef struct bh_mpc_common bh_mpc_common;
 typedef struct bh_mpc_common_contrib bh_mpc_common_contrib;
 typedef struct bh_mpc_uncommon bh_mpc_uncommon;
@@ -635,6 +670,9 @@ bh_status bh_mpc_common_vector(const bh_mpc_common* storage, int which, const bh
 bh_status bh_mpc_common_point(const bh_mpc_common* storage, int which, uint8_t* out);
 bh_status bh_mpc_common_write(const bh_mpc_common* storage, uint8_t* out, size_t cap, size_t* written);
 bh_status bh_mpc_common_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_mpc_common** out);
+bh_status bh_mpc_common_write_compressed(const bh_mpc_common* storage, uint8_t* out, size_t cap, size_t* written);
+bh_status bh_mpc_common_read_compressed(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                        bh_mpc_common** out);
 bh_status bh_mpc_common_contrib_free(bh_mpc_common_contrib* contrib);
 bh_status bh_mpc_common_contrib_vector(const bh_mpc_common_contrib* contrib, int which, int mine, const bh_srs** out);
 bh_status bh_mpc_common_contrib_point(const bh_mpc_common_contrib* contrib, int which, uint8_t* out);
@@ -642,6 +680,10 @@ bh_status bh_mpc_common_contrib_write(const bh_mpc_common_contrib* contrib, uint
                                       size_t* written);
 bh_status bh_mpc_common_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
                                      bh_mpc_common_contrib** out);
+bh_status bh_mpc_common_contrib_write_compressed(const bh_mpc_common_contrib* contrib, uint8_t* out, size_t cap,
+                                                 size_t* written);
+bh_status bh_mpc_common_contrib_read_compressed(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                                bh_mpc_common_contrib** out);
 bh_status bh_mpc_uncommon_initial(bh_ctx* ctx, const bh_srs* front_g1, const bh_srs* front_g2, const bh_srs* back_g1,
                                   const bh_srs* back_g2, const bh_srs* h_g1, const bh_srs* h_g2,
                                   bh_mpc_uncommon** out);
@@ -655,6 +697,9 @@ bh_status bh_mpc_uncommon_vector(const bh_mpc_uncommon* storage, int which, cons
 bh_status bh_mpc_uncommon_point(const bh_mpc_uncommon* storage, int which, uint8_t* out);
 bh_status bh_mpc_uncommon_write(const bh_mpc_uncommon* storage, uint8_t* out, size_t cap, size_t* written);
 bh_status bh_mpc_uncommon_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_mpc_uncommon** out);
+bh_status bh_mpc_uncommon_write_compressed(const bh_mpc_uncommon* storage, uint8_t* out, size_t cap, size_t* written);
+bh_status bh_mpc_uncommon_read_compressed(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                          bh_mpc_uncommon** out);
 bh_status bh_mpc_uncommon_contrib_free(bh_mpc_uncommon_contrib* contrib);
 bh_status bh_mpc_uncommon_contrib_vector(const bh_mpc_uncommon_contrib* contrib, int which, int mine,
                                          const bh_srs** out);
@@ -663,6 +708,10 @@ bh_status bh_mpc_uncommon_contrib_write(const bh_mpc_uncommon_contrib* contrib, 
                                         size_t* written);
 bh_status bh_mpc_uncommon_contrib_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
                                        bh_mpc_uncommon_contrib** out);
+bh_status bh_mpc_uncommon_contrib_write_compressed(const bh_mpc_uncommon_contrib* contrib, uint8_t* out,
+                                                   size_t cap, size_t* written);
+bh_status bh_mpc_uncommon_contrib_read_compressed(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked,
+                                                  bh_mpc_uncommon_contrib** out);
 /* ---- between the rounds: CommonParamterInStorage::matrix (mpc.rs:597-645) for ANY circuit, and
  * the Parameters of the finished ceremony (generate_parameters_mpc, generator.rs:163-237, whose a,
  * b_g1 and b_g2 the reference leaves empty).
