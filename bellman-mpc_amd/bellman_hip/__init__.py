@@ -207,6 +207,17 @@ def _load():
         "bh_verify_each_device": (I, [P, P, S, P, P, S, S, P, P]),
         "bh_verify_batch_device": (I, [P, P, S, P, P, S, S, P, P]),
         "bh_proofs_decode": (I, [P, P, S, P, P, P, P]),
+        "bh_gt_pairing": (I, [P, P, S, P, S, S, P]),
+        "bh_gt_from_miller": (I, [P, P, S, P]),
+        "bh_gt_upload": (I, [P, P, S, I, P]),
+        "bh_gt_read": (I, [P, S, S, P]),
+        "bh_gt_len": (S, [P]),
+        "bh_gt_free": (I, [P]),
+        "bh_gt_add": (I, [P, P, P, P]),
+        "bh_gt_neg": (I, [P, P, P]),
+        "bh_gt_mul_each": (I, [P, P, P, S, P]),
+        "bh_gt_sum": (I, [P, P, P]),
+        "bh_gt_multiexp": (I, [P, P, P, P]),
     }
     for kind in ("common", "uncommon"):
         for who in ("", "_contrib"):
@@ -255,6 +266,8 @@ EXPORTED_SYMBOLS = [
     "bh_mpc_parameters", "bh_mpc_last_matrix_ms", "bh_final_exponentiation_batch", "bh_verify_each_device",
     "bh_mpc_common_check", "bh_mpc_common_verify_structure", "bh_mpc_last_check_ms",
     "bh_srs_upload_compressed", "bh_srs_read_compressed",
+    "bh_gt_pairing", "bh_gt_from_miller", "bh_gt_upload", "bh_gt_read", "bh_gt_len", "bh_gt_free", "bh_gt_add",
+    "bh_gt_neg", "bh_gt_mul_each", "bh_gt_sum", "bh_gt_multiexp",
 ] + [f"bh_mpc_{kind}{who}_{op}" for kind in ("common", "uncommon") for who in ("", "_contrib")
      for op in ("free", "vector", "point", "write", "read", "write_compressed", "read_compressed")]
 BH_VEC_H, BH_VEC_L, BH_VEC_A, BH_VEC_B_G1, BH_VEC_B_G2 = range(5)
@@ -1630,6 +1643,127 @@ def pairing_product_is_one(ctx, g1_bases, g2_bases):
     """prod_i e(g1_bases[i], g2_bases[i]) == 1 for two device vectors of one length."""
     assert len(g1_bases) == len(g2_bases)
     return final_exponentiation(multi_miller_loop(ctx, g1_bases, g2_bases)) == [(1, 0)] + [(0, 0)] * 5
+
+
+# ------------------------------------------------------------------ Gt vectors (gt_bytes.rs)
+GT_BYTES = 576
+_GT_ORDER = (5, 3, 1, 4, 2, 0)  # gt_format's coefficients: w^5, w^3, w^1, w^4, w^2, w^0, each c1 then c0
+
+
+def gt_format(f):
+    """Six pairs of ints, the Fp2 coefficients of w^0..w^5 of a value in the crate's convention ->
+    its 576 bytes (gt_bytes.rs:32-74)."""
+    return b"".join(int(f[k][1]).to_bytes(48, "big") + int(f[k][0]).to_bytes(48, "big") for k in _GT_ORDER)
+
+
+def gt_parse(b):
+    """gt_format's inverse (no range check: the library's upload makes it)."""
+    assert len(b) == GT_BYTES
+    f = [None] * 6
+    for q, k in enumerate(_GT_ORDER):
+        f[k] = (int.from_bytes(b[96 * q + 48:96 * q + 96], "big"), int.from_bytes(b[96 * q:96 * q + 48], "big"))
+    return f
+
+
+def _scalar_words(scalars):
+    return np.ascontiguousarray(np.stack([fr_canonical_words(x) for x in scalars]) if len(scalars)
+                                else np.zeros((1, 4), np.uint64))
+
+
+class Gt:
+    """A device-resident vector of Gt values with the reference's operators (gt_utils.rs):
+    a + b, -a, a * scalars."""
+
+    def __init__(self, ctx, handle):
+        self.h, self.ctx = handle, ctx
+
+    @classmethod
+    def from_miller(cls, ctx, values):
+        """multi_miller_loop values (lists of six coefficient pairs) -> the Gt values they stand
+        for: conj(f^((p^12 - 1) / r))^3 (bh_gt_from_miller)."""
+        n = len(values)
+        src = np.frombuffer(b"".join(_f12_to_bytes(f) for f in values) or b"\0", dtype=np.uint8)
+        h = ctypes.c_void_p()
+        _check(_lib.bh_gt_from_miller(ctx.h, _ptr(src), n, ctypes.byref(h)), "bh_gt_from_miller")
+        return cls(ctx, h)
+
+    @classmethod
+    def from_bytes(cls, ctx, data: bytes, checked=True):
+        """len(data) / 576 values in gt_format (bh_gt_upload); checked adds the membership test."""
+        assert len(data) % GT_BYTES == 0
+        n = len(data) // GT_BYTES
+        buf = np.frombuffer(data, dtype=np.uint8) if n else np.zeros(1, np.uint8)
+        h = ctypes.c_void_p()
+        _check(_lib.bh_gt_upload(ctx.h, _ptr(buf), n, int(checked), ctypes.byref(h)), "bh_gt_upload")
+        return cls(ctx, h)
+
+    def __len__(self):
+        return _lib.bh_gt_len(self.h)
+
+    def read(self, first=0, n=None):
+        """Elements first .. first + n (default: the rest) as gt_format bytes."""
+        if n is None:
+            n = len(self) - first
+        out = np.zeros(max(n, 1) * GT_BYTES, dtype=np.uint8)
+        _check(_lib.bh_gt_read(self.h, first, n, _ptr(out)), "bh_gt_read")
+        return out[:n * GT_BYTES].tobytes()
+
+    def to_bytes(self):
+        return self.read()
+
+    def __add__(self, other):
+        h = ctypes.c_void_p()
+        _check(_lib.bh_gt_add(self.ctx.h, self.h, other.h, ctypes.byref(h)), "bh_gt_add")
+        return Gt(self.ctx, h)
+
+    def __neg__(self):
+        h = ctypes.c_void_p()
+        _check(_lib.bh_gt_neg(self.ctx.h, self.h, ctypes.byref(h)), "bh_gt_neg")
+        return Gt(self.ctx, h)
+
+    def __mul__(self, scalars):
+        """gt * Scalar: a list of ints below r, one per element, or one int for every element."""
+        if isinstance(scalars, int):
+            scalars = [scalars]
+        h = ctypes.c_void_p()
+        _check(_lib.bh_gt_mul_each(self.ctx.h, self.h, _ptr(_scalar_words(scalars)), len(scalars), ctypes.byref(h)),
+               "bh_gt_mul_each")
+        return Gt(self.ctx, h)
+
+    def sum(self):
+        """The sum of all elements (one for none), as gt_format bytes."""
+        out = np.zeros(GT_BYTES, dtype=np.uint8)
+        _check(_lib.bh_gt_sum(self.ctx.h, self.h, _ptr(out)), "bh_gt_sum")
+        return out.tobytes()
+
+    def close(self):
+        if self.h is not None:
+            _lib.bh_gt_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pairing(ctx, g1_bases, g2_bases, off1=0, off2=0, n=None):
+    """The Gt vector of pairing(g1_bases[off1 + i], g2_bases[off2 + i]), i < n (default: the rest
+    of g1_bases), the crate's values (bh_gt_pairing)."""
+    if n is None:
+        n = len(g1_bases) - off1
+    h = ctypes.c_void_p()
+    _check(_lib.bh_gt_pairing(ctx.h, g1_bases.h, off1, g2_bases.h, off2, n, ctypes.byref(h)), "bh_gt_pairing")
+    return Gt(ctx, h)
+
+
+def multiexp_gt(ctx, gt, scalars):
+    """sum_i scalars[i] * gt[i] as gt_format bytes (bh_gt_multiexp)."""
+    assert len(scalars) == len(gt)
+    out = np.zeros(GT_BYTES, dtype=np.uint8)
+    _check(_lib.bh_gt_multiexp(ctx.h, gt.h, _ptr(_scalar_words(scalars)), _ptr(out)), "bh_gt_multiexp")
+    return out.tobytes()
 
 
 def device_count():

@@ -237,6 +237,10 @@ extern "C" bh_status bh_selftest_density_index(int device, const uint64_t* words
 // (1..16), so that small inputs reach a lane's batch edge, the wave edge and a short last lane
 extern "C" bh_status bh_selftest_miller_product(bh_ctx* ctx, const bh_srs* g1, size_t off1, const bh_srs* g2,
                                                 size_t off2, size_t n, int K, uint8_t out[576]);
+// gt.hip (tests/test_gpu_gt.py): the cyclotomic-squaring formula of k_gt_cyc_sqr on n arbitrary
+// canonical Fp12 values, in and out in bh_miller_product's 576-byte encoding (a polynomial map, so
+// the model predicts it for any input; a coefficient >= p: BH_ERR_INVALID_ENCODING)
+extern "C" bh_status bh_selftest_gt_cyclotomic_square(bh_ctx* ctx, const uint8_t* in, size_t n, uint8_t* out);
 // proofs_dev.hip (tests/test_gpu_verify_device.py): the square-root routine the proof decode
 // kernels call, on n caller-chosen canonical values (field 1: Fp, 12 LE words each; 2: Fp2, c0 then
 // c1; a value >= p: BH_ERR_INVALID_ARGUMENT).  out per value: the is-square flag (1 / 0), then the

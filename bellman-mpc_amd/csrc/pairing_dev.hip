@@ -48,6 +48,7 @@
 #include <algorithm>
 #include <memory>
 
+#include "f12_dev.cuh"
 #include "final_exp_chain.h"
 #include "group_host.h"
 #include "pairing_dev.h"
@@ -58,80 +59,12 @@ namespace bh {
 
 namespace {
 
-using F2 = Fp2Ops;
-constexpr int FW = 144;  // packed words of an Fp12 value: c[0].c0, c[0].c1, ..., c[5].c1, 12 each
 constexpr int TW = 48;   // of a T record: x.c0, x.c1, y.c0, y.c1
 constexpr int SW = 24;   // of a prefix product
 constexpr uint64_t MILLER_X_ABS = 0xd201000000010000ull;
 
-// ---------------------------------------------------------------- word-major lane storage
-__device__ __forceinline__ DFp2 ld_fp2(const uint32_t* base, size_t stride, size_t lane, int word0) {
-  uint32_t w[24];
-#pragma unroll
-  for (int j = 0; j < 24; j++) w[j] = base[(size_t)(word0 + j) * stride + lane];
-  return F2::unpack(w);
-}
-// x < 2^384 (8p): every caller stores a product (< 2p) or a fully reduced value
-__device__ __forceinline__ void st_fp2(uint32_t* base, size_t stride, size_t lane, int word0, const DFp2& x) {
-  uint32_t w[24];
-  F2::pack(x, w);
-#pragma unroll
-  for (int j = 0; j < 24; j++) base[(size_t)(word0 + j) * stride + lane] = w[j];
-}
-
-// (a + bu)^-1 = (a - bu) / (a^2 + b^2), the inversion in Fp by Fermat: crs.hip's Inv<Fp2Ops> (a
-// device function cannot be shared between translation units built without relocatable device code)
-__device__ DFp2 fp2_inv(const DFp2& x) {
-  // p - 2, little-endian 32-bit words
-  constexpr uint32_t E[12] = {0xffffaaa9u, 0xb9feffffu, 0xb153ffffu, 0x1eabfffeu, 0xf6b0f624u, 0x6730d2a0u,
-                              0xf38512bfu, 0x64774b84u, 0x434bacd7u, 0x4b1ba7b6u, 0x397fe69au, 0x1a0111eau};
-  const DFp t = fe_add<FpCfg>(fe_sqr<FpCfg>(x.c0), fe_sqr<FpCfg>(x.c1));
-  DFp r = fe_one<FpCfg>();
-#pragma unroll 1
-  for (int w = 11; w >= 0; w--) {
-#pragma unroll 1
-    for (int b = 31; b >= 0; b--) {
-      r = fe_sqr<FpCfg>(r);
-      if ((E[w] >> b) & 1u) r = fe_mul<FpCfg>(r, t);
-    }
-  }
-  DFp2 o;
-  o.c0 = fe_mul<FpCfg>(x.c0, r);
-  o.c1 = fe_mul<FpCfg>(fe_neg<FpCfg, 2>(x.c1), r);  // x.c1 < 2p at both call sites
-  return o;
-}
-
 // ---------------------------------------------------------------- Fp12 products
-// (U + xi W) for the unwrapped part U and the part W that wrapped past w^6 = xi = 1 + u:
-// xi W = (W0 - W1) + (W0 + W1) u.  WK: W's components are < WK p.
-template <uint32_t WK>
-__device__ __forceinline__ DFp2 fold_xi(const DFp2& U, const DFp2& W) {
-  DFp2 c;
-  c.c0 = fe_add<FpCfg>(U.c0, fe_sub<FpCfg, WK>(W.c0, W.c1));
-  c.c1 = fe_add<FpCfg>(U.c1, fe_add<FpCfg>(W.c0, W.c1));
-  return c;
-}
-
-// out[io] = a[ia] * b[ib], all coefficients: c_k = sum_i a_i b_(k-i mod 6), the terms with i > k
-// times xi.  out must not be a or b's buffer.  Bounds: U sums <= 6 products (< 12p), W <= 5
-// (< 10p, so fe_sub<16>); the folded coefficient is < 12p + 10p + 16p = 38p < 128p (reduce).
-__device__ void f12_mul_dense(const uint32_t* a, size_t ia, const uint32_t* b, size_t ib, uint32_t* out, size_t io,
-                              size_t stride) {
-#pragma unroll 1
-  for (int k = 0; k < 6; k++) {
-    DFp2 U = F2::zero(), W = F2::zero();
-#pragma unroll 1
-    for (int i = 0; i < 6; i++) {
-      const bool wrap = i > k;
-      const int j = wrap ? k - i + 6 : k - i;
-      const DFp2 prod = F2::mul(ld_fp2(a, stride, ia, 24 * i), ld_fp2(b, stride, ib, 24 * j));
-      if (wrap) W = F2::add(W, prod);
-      else U = F2::add(U, prod);
-    }
-    st_fp2(out, stride, io, 24 * k, F2::reduce(fold_xi<16>(U, W)));
-  }
-}
-
+// (ld_fp2, st_fp2, fp2_inv, fold_xi and f12_mul_dense: f12_dev.cuh)
 // out = a * (l0 + l2 w^2 + yp w^3), yp in Fp: c_k = a_k l0 + a_(k-2) l2 + a_(k-3) yp with the
 // same wrap.  Bounds: l0 < 3p, l2 <= 2p, yp < p and a's coefficients < p, every product < 2p;
 // U sums <= 3 products (< 6p), W <= 2 (< 4p, so fe_sub<4>); folded < 6p + 4p + 4p = 14p (reduce).
@@ -424,14 +357,16 @@ inline unsigned nb64(size_t n) { return (unsigned)((n + 63) / 64); }
 // library's longest (k_varbase_mul_win<G2>, 147 ms per 2^20); DESIGN.md section 11 has the
 // measured figure.
 constexpr int MILLER_BITS_PER_LAUNCH = 8;
-// pairs per call of the loop (the workspace: 752 B per pair at K = 16, plus 1.7 KB per lane)
-constexpr size_t MILLER_CHUNK = (size_t)1 << 20;
+
+}  // namespace
 
 Fp12 f12_from_dev_words(const uint32_t* w) {
   Fp12 r;
   for (int i = 0; i < 6; i++) r.c[i] = Fp2{fp_from_dev_words(w + 24 * i), fp_from_dev_words(w + 24 * i + 12)};
   return r;
 }
+
+namespace {
 
 // Pairs per lane.  A lane's step costs one inversion (460 Fp products) plus about 120 per pair, so
 // a larger K does less work per pair, but only lanes run in parallel: while the lanes of K = 1
@@ -449,15 +384,9 @@ int choose_k(bh_ctx* ctx, size_t n) {
   return (int)std::min<size_t>(MILLER_MAX_K, std::max<size_t>(1, (n + resident - 1) / resident));
 }
 
-// The loop's device state of one call.  f: fslots >= 2 Fp12 buffers of FW * stride words each, the
-// first two the loop's double buffer; miller_lanes leaves every lane's value in the first.
-struct MillerWork {
-  DevBuf f, T, S, mask, flag;
-  size_t lanes = 0, stride = 0;
-};
+}  // namespace
 
-// lane l's value prod_{k < K} f(g1[l K + k], g2[l K + k]) for the lanes of n pairs, left on the
-// device in w->f; returns synchronised.  BH_ERR_PAIRING_DEGENERATE: a step met a zero denominator.
+// (MillerWork and the contract: pairing_dev.h)
 bh_status miller_lanes(bh_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size_t n, int K, int fslots,
                        MillerWork* w) {
   MillerArgs A;
@@ -493,19 +422,11 @@ bh_status miller_lanes(bh_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size
   return hflag ? BH_ERR_PAIRING_DEGENERATE : BH_OK;
 }
 
-bh_status miller_chunk(bh_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size_t n, int K, Fp12* out) {
-  MillerWork w;
-  bh_status s = miller_lanes(ctx, g1, g2, n, K, 2, &w);
-  if (s) return s;
-  uint32_t* f = w.f.as<uint32_t>();
-  const size_t stride = w.stride;
-  DevBuf pong;
-  BH_TRY_HIP(pong.alloc((size_t)FW * stride * 4));
-  size_t m = w.lanes;
+bh_status f12_lanes_product(bh_ctx* ctx, uint32_t* f, uint32_t* ping, uint32_t* pong, size_t stride, size_t m,
+                            Fp12* out) {
   while (m > 64) {
     const size_t o = (m + 7) / 8;
-    hipLaunchKernelGGL(k_f12_product, dim3(nb64(o)), dim3(64), 0, ctx->stream, f, f + (size_t)FW * stride,
-                       pong.as<uint32_t>(), stride, m, o);
+    hipLaunchKernelGGL(k_f12_product, dim3(nb64(o)), dim3(64), 0, ctx->stream, f, ping, pong, stride, m, o);
     BH_TRY_HIP(hipGetLastError());
     m = o;
   }
@@ -521,12 +442,26 @@ bh_status miller_chunk(bh_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size
   return BH_OK;
 }
 
+namespace {
+
+bh_status miller_chunk(bh_ctx* ctx, const uint32_t* g1, const uint32_t* g2, size_t n, int K, Fp12* out) {
+  MillerWork w;
+  bh_status s = miller_lanes(ctx, g1, g2, n, K, 2, &w);
+  if (s) return s;
+  uint32_t* f = w.f.as<uint32_t>();
+  DevBuf pong;
+  BH_TRY_HIP(pong.alloc((size_t)FW * w.stride * 4));
+  return f12_lanes_product(ctx, f, f + (size_t)FW * w.stride, pong.as<uint32_t>(), w.stride, w.lanes, out);
+}
+
 void f12_to_bytes(const Fp12& f, uint8_t out[576]) {
   for (int i = 0; i < 6; i++) {
     fp_to_be(f.c[i].c0, out + 96 * i);
     fp_to_be(f.c[i].c1, out + 96 * i + 48);
   }
 }
+
+}  // namespace
 
 // host Montgomery (R = 2^384) -> the device's packed words (the canonical value of c * 2^406)
 void fp_to_dev_words(const Fp& x, uint32_t* w) {
@@ -549,13 +484,7 @@ void fp_to_dev_words(const Fp& x, uint32_t* w) {
 // lane count from there.
 constexpr int FEXP_PRODUCTS_PER_LAUNCH = 8;
 
-// The chain in place on slot 0 of ws (FE_SLOTS * FW * stride words), enqueued on ctx->stream; the
-// tables must outlive the enqueued work (the caller synchronises before dropping them).
-struct FexpTables {
-  DevBuf prog, consts;
-  std::vector<std::pair<int, int>> launches;
-};
-
+// (FexpTables and the contract of the two functions: pairing_dev.h)
 bh_status fexp_tables(bh_ctx* ctx, FexpTables* t) {
   const std::vector<FeStep>& p = fe_program();
   const FeConsts& C = fe_consts();
@@ -595,6 +524,8 @@ bh_status fexp_enqueue(bh_ctx* ctx, const FexpTables& t, uint32_t* ws, size_t n,
   }
   return BH_OK;
 }
+
+namespace {
 
 // a coefficient >= p among the 12 n big-endian 48-byte values
 bool f12_bytes_canonical(const uint8_t* f, size_t n) {

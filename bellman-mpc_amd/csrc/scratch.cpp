@@ -20,6 +20,7 @@
 #include "api_internal.h"
 #include "dist_h.h"
 #include "group_fft.h"
+#include "gt.h"
 #include "pairing_dev.h"
 #include "point_codec.h"
 #include "proofs_dev.h"
@@ -98,6 +99,7 @@ bh_status scratch_report(bh_ctx* ctx, uint64_t out[10], std::string* worst) {
   proofs_kernels(ks);
   point_codec_kernels(ks);
   verify_each_kernels(ks);
+  gt_kernels(ks);
   const uint64_t cus = (uint64_t)std::max(prop.multiProcessorCount, 1);
   const uint64_t slots_per_cu = 32;  // KFD max_slots_scratch_cu (profiles/r03_kfd_queue_props.txt)
   // per queue: at the scratch-slot bound (what the runtime may reserve for a large dispatch:

@@ -790,6 +790,48 @@ bh_status bh_final_exponentiation(const uint8_t f[576], uint8_t out[576]);
  * out may be f. */
 bh_status bh_final_exponentiation_batch(bh_ctx* ctx, const uint8_t* f, size_t n, uint8_t* out);
 
+/* ---- vectors of target-group values (the fork's gt_bytes.rs / gt_utils.rs: pairing(g1, g2),
+ * gt + gt, gt * Scalar, -gt as 576-byte strings).  A bh_gt is a vector of n Gt values resident on
+ * the context's device, in the convention of the bls12_381 crate: with e0(P, Q) the final
+ * exponentiation of the Miller value above, a bh_gt element is conj(e0(P, Q))^3.
+ * gt_format (gt_bytes.rs:32-74), the byte form of every entry point below: the six Fp2 coefficients
+ * of w^5, w^3, w^1, w^4, w^2, w^0 in that order, each c1 then c0, each Fp 48 bytes big-endian
+ * canonical.
+ * Common rules: a null pointer, a handle of another device than ctx's or a range past a vector's end
+ * is BH_ERR_INVALID_ARGUMENT; n = 0 is BH_OK and gives an empty vector; on any error no handle is
+ * returned.  Every returned bh_gt is freed by the caller.
+ *   pairing      out[i] = pairing(g1[off1 + i], g2[off2 + i]) (gt_bytes.rs:210), i < n; a pair with
+ *                an identity on either side gives one.  Ranges, groups and
+ *                BH_ERR_PAIRING_DEGENERATE as the Miller product above; no vector is made then.
+ *   from_miller  f: n x 576 bytes in the Miller product's encoding; out[i] =
+ *                conj(f_i^((p^12 - 1) / r))^3, so that products built with the calls above become Gt
+ *                values.  A coefficient >= p: BH_ERR_INVALID_ENCODING.
+ *   upload       n x 576 bytes of gt_format.  A coefficient >= p is always
+ *                BH_ERR_INVALID_ENCODING.  checked adds membership: frob^4(f) f = frob^2(f), then
+ *                f^r = 1; a failure is BH_ERR_NOT_IN_SUBGROUP.  Unchecked values outside Gt give
+ *                unspecified results in the calls below, never a fault.
+ *   read         elements first .. first + n as gt_format bytes.
+ *   add          elementwise gt + gt, the Fp12 product; the lengths must be equal.
+ *   neg          -gt, the conjugate.
+ *   mul_each     gt * Scalar with canonical Fr scalars (4 little-endian u64 each); n_scalars is the
+ *                length of a, or 1 for one scalar applied to every element.  A scalar >= r:
+ *                BH_ERR_INVALID_ARGUMENT.  A zero scalar gives one.
+ *   sum          the sum of all elements as gt_format bytes; none gives one.
+ *   multiexp     sum_i scalars[i] a[i] (one scalar per element): mul_each, then sum. */
+typedef struct bh_gt bh_gt;
+bh_status bh_gt_pairing(bh_ctx* ctx, const bh_srs* g1, size_t off1, const bh_srs* g2, size_t off2, size_t n,
+                        bh_gt** out);
+bh_status bh_gt_from_miller(bh_ctx* ctx, const uint8_t* f, size_t n, bh_gt** out);
+bh_status bh_gt_upload(bh_ctx* ctx, const uint8_t* bytes, size_t n, int checked, bh_gt** out);
+bh_status bh_gt_read(const bh_gt* gt, size_t first, size_t n, uint8_t* out);
+size_t bh_gt_len(const bh_gt* gt);
+bh_status bh_gt_free(bh_gt* gt);
+bh_status bh_gt_add(bh_ctx* ctx, const bh_gt* a, const bh_gt* b, bh_gt** out);
+bh_status bh_gt_neg(bh_ctx* ctx, const bh_gt* a, bh_gt** out);
+bh_status bh_gt_mul_each(bh_ctx* ctx, const bh_gt* a, const uint64_t* scalars, size_t n_scalars, bh_gt** out);
+bh_status bh_gt_sum(bh_ctx* ctx, const bh_gt* a, uint8_t out[576]);
+bh_status bh_gt_multiexp(bh_ctx* ctx, const bh_gt* a, const uint64_t* scalars, uint8_t out[576]);
+
 /* ---- batch verification on the device (verifier/batch.rs:95-169).
  * bh_verify_batch_device: for every input the status and *valid of bh_verify_batch, with the
  * per-proof work on the context's device: Proof::read of the k proofs (bh_proofs_decode's kernels),
