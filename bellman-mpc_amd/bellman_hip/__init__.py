@@ -195,6 +195,8 @@ def _load():
         "bh_mpc_common_check": (I, [P, P, P, P, P]),
         "bh_mpc_common_verify_structure": (I, [P, P, P, P, P, P, P]),
         "bh_mpc_last_check_ms": (None, [P]),
+        "bh_params_check": (I, [P, P, P, P, P, P, P, P]),
+        "bh_params_last_check_ms": (None, [P]),
         "bh_mpc_common_len": (S, [P]),
         "bh_mpc_uncommon_initial": (I, [P, P, P, P, P, P, P, P]),
         "bh_mpc_uncommon_contribute": (I, [P, P, P, P, P]),
@@ -265,6 +267,7 @@ EXPORTED_SYMBOLS = [
     "bh_srs_fft", "bh_srs_read", "bh_mpc_common_matrix", "bh_mpc_matrix_vector", "bh_mpc_matrix_free",
     "bh_mpc_parameters", "bh_mpc_last_matrix_ms", "bh_final_exponentiation_batch", "bh_verify_each_device",
     "bh_mpc_common_check", "bh_mpc_common_verify_structure", "bh_mpc_last_check_ms",
+    "bh_params_check", "bh_params_last_check_ms",
     "bh_srs_upload_compressed", "bh_srs_read_compressed",
     "bh_gt_pairing", "bh_gt_from_miller", "bh_gt_upload", "bh_gt_read", "bh_gt_len", "bh_gt_free", "bh_gt_add",
     "bh_gt_neg", "bh_gt_mul_each", "bh_gt_sum", "bh_gt_multiexp",
@@ -915,6 +918,18 @@ class Parameters:
     def vector(self, which):
         """ParameterSource::get_h/get_l/get_a/get_b_g1/get_b_g2: BH_VEC_* -> multiexp bases."""
         return ParamsBases(self, which)
+
+    def check(self, r1cs, storage, rho=None, sigma=None):
+        """bh_params_check: the mask of failed equations (BH_PARAMS_CHECK_*), 0 iff these Parameters
+        are what the generator gives for r1cs and the scalars of the WELL-FORMED round-one storage
+        (the initial one, or one whose check() returned 0), for some gamma and delta.  rho, sigma:
+        two independent nonzero scalars below r (default: fresh random ones)."""
+        valid, mask = ctypes.c_int(), ctypes.c_uint32()
+        _check(_lib.bh_params_check(self.ctx.h, self.h, r1cs.h, storage.h, _ptr(_rho_words(rho)),
+                                    _ptr(_rho_words(sigma)), ctypes.byref(valid), ctypes.byref(mask)),
+               "bh_params_check")
+        assert bool(valid.value) == (mask.value == 0)
+        return mask.value
 
     def prepare(self, witness, nshards=1):
         """Build the prover window tables now rather than inside the first proof."""
@@ -1833,6 +1848,10 @@ BH_MPC_MATRIX_A, BH_MPC_MATRIX_B_G1, BH_MPC_MATRIX_B_G2 = 6, 7, 8
  BH_MPC_CHECK_ALPHA_TAU, BH_MPC_CHECK_ALPHA_TAU_G2, BH_MPC_CHECK_BETA_TAU, BH_MPC_CHECK_BETA_TAU_G2,
  BH_MPC_CHECK_LENGTHS, BH_MPC_CHECK_ALPHA_RATIO, BH_MPC_CHECK_BETA_RATIO, BH_MPC_CHECK_TAU_RATIO) = (
     1 << k for k in range(13))
+# bits of bh_params_check's mask
+(BH_PARAMS_CHECK_SIZES, BH_PARAMS_CHECK_ALPHA, BH_PARAMS_CHECK_BETA, BH_PARAMS_CHECK_DELTA, BH_PARAMS_CHECK_A,
+ BH_PARAMS_CHECK_B_G1, BH_PARAMS_CHECK_B_G2, BH_PARAMS_CHECK_L, BH_PARAMS_CHECK_IC, BH_PARAMS_CHECK_H) = (
+    1 << k for k in range(10))
 
 
 class _MpcHandle:
@@ -2045,6 +2064,13 @@ def last_check_ms():
     """(weights and multiexps, pairings): wall ms of this thread's last structure check."""
     out = (ctypes.c_double * 2)()
     _lib.bh_mpc_last_check_ms(out)
+    return tuple(out)
+
+
+def last_params_check_ms():
+    """(scalar side, multiexps, pairings): wall ms of this thread's last Parameters.check."""
+    out = (ctypes.c_double * 3)()
+    _lib.bh_params_last_check_ms(out)
     return tuple(out)
 
 

@@ -15,7 +15,8 @@
 // caller's random z_i over verify.cpp's Miller loop.  The structure check
 // (bh_mpc_common_check, bh_mpc_common_verify_structure) is not in the
 // reference: it shows that a round-one storage is a power sequence, with the multiexp, the
-// power-scalar kernel and the host pairing that are already here.
+// power-scalar kernel and the host pairing that are already here.  bh_params_check (DESIGN.md
+// section 19) closes the chain the same way: Parameters against a circuit and such a storage.
 #include <stdlib.h>
 #include <string.h>
 
@@ -25,6 +26,7 @@
 #include "group_fft.h"
 #include "pairing.h"
 #include "pairing_dev.h"
+#include "params_check.h"
 #include "point_codec.h"
 #include "r1cs.h"
 #include "varbase.h"
@@ -565,6 +567,7 @@ thread_local double g_miller_ms = 0;
 thread_local int g_miller_device = 0;
 thread_local double g_matrix_ms[3] = {0, 0, 0};
 thread_local double g_check_ms[2] = {0, 0};
+thread_local double g_pcheck_ms[3] = {0, 0, 0};
 
 double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1088,6 +1091,124 @@ bh_status bh_mpc_parameters(bh_ctx* ctx, const bh_mpc_common* round1, const bh_m
   BH_TRY_HIP(hipStreamSynchronize(ctx->stream));
   *out = p.release();
   return BH_OK;
+}
+
+// ================================================================ Parameters against circuit and storage
+// DESIGN.md section 19.  The scalars are params_check.hip's, resident; the multiexps msm_device's
+// on them, one after another on the context's stream; the pairings the host pool's, as in
+// structure_mask.  generator.rs:520-572 (the queries), 614-633 (the identity filter)
+bh_status bh_params_check(bh_ctx* ctx, const bh_params* p, const bh_r1cs* r, const bh_mpc_common* st,
+                          const uint64_t rho[4], const uint64_t sigma[4], int* valid, uint32_t* failed) {
+  if (!ctx || !p || !r || !st || !valid || !check_weight(rho) || !check_weight(sigma)) return BH_ERR_INVALID_ARGUMENT;
+  if (!p->ctx || p->ctx->device != ctx->device || r->device != ctx->device || st->ctx->device != ctx->device)
+    return BH_ERR_INVALID_ARGUMENT;
+  const size_t m = r->m, ni = r->ni, na = r->na;
+  if (m < 2 || st->v[0]->n < 2 * m) return BH_ERR_INVALID_ARGUMENT;
+  *valid = 0;
+  if (failed) *failed = 0;
+  MPC_ENTER(ctx);
+  for (double& x : g_pcheck_ms) x = 0;
+  uint32_t mask = 0;
+  auto done = [&] {
+    if (failed) *failed = mask;
+    *valid = mask == 0;
+    return BH_OK;
+  };
+  if (p->ic.size() != ni || p->l.n != na || p->h.n != m - 1 || p->b_g1.n != p->b_g2.n) {
+    mask = BH_PARAMS_CHECK_SIZES;
+    return done();
+  }
+  auto t0 = std::chrono::steady_clock::now();
+  ParamsCheckScalars sc;
+  bh_status s = params_check_scalars(ctx, r, fr_from_canonical(rho), fr_from_canonical(sigma), &sc);
+  if (s) return s;
+  g_pcheck_ms[0] = ms_since(t0);
+  if (p->a.n != sc.n_a || p->b_g1.n != sc.n_b) {
+    mask = BH_PARAMS_CHECK_SIZES;
+    return done();
+  }
+  // ---- the multiexps: 13 in G1 (14 with ic's), 2 in G2
+  t0 = std::chrono::steady_clock::now();
+  const bh_srs *T = st->v[0].get(), *T2 = st->v[1].get(), *AT = st->v[2].get(), *BT = st->v[4].get();
+  auto g1 = [&](const bh_srs* b, const uint32_t* d, size_t len, Jac<Fp>* o) {
+    return msm_device<G1Host>(ctx, b, 0, d, len, nullptr, o, nullptr);
+  };
+  auto g2 = [&](const bh_srs* b, const uint32_t* d, size_t len, Jac<Fp2>* o) {
+    return msm_device<G2Host>(ctx, b, 0, d, len, nullptr, o, nullptr);
+  };
+  const uint32_t* w = sc.w.as<uint32_t>();
+  const uint32_t* hw = sc.hw.as<uint32_t>();
+  Jac<Fp> a_l, a_r, b1_l, b1_r, l_l, ic_l, h_l, h_r, k[2];
+  Jac<Fp2> b2_l, b2_r;
+  // the left-hand sides, over the Parameters
+  if ((s = g1(&p->a, sc.wa.as<uint32_t>(), sc.n_a, &a_l))) return s;
+  if ((s = g1(&p->b_g1, sc.wb.as<uint32_t>(), sc.n_b, &b1_l))) return s;
+  if ((s = g2(&p->b_g2, sc.wb.as<uint32_t>(), sc.n_b, &b2_l))) return s;
+  if ((s = g1(&p->l, w + ni * 8, na, &l_l))) return s;
+  if ((s = g1(&p->h, hw + m * 8, m - 1, &h_l))) return s;
+  {
+    // ic lives on the host.  An identity among it (a zero ic scalar, which the generator writes as
+    // one) has no device record: the generator stands in for it and its share is taken off again
+    std::vector<AffinePt<Fp>> ic = p->ic;
+    Jac<Fp> off = jac_identity<Fp>();
+    const Fr rho_fr = fr_from_canonical(rho);
+    for (size_t j = 0; j < ni; j++) {
+      if (!ic[j].infinity) continue;
+      ic[j] = g1_gen();
+      const uint64_t e = j;
+      uint64_t wj[4];
+      fr_to_canonical(pow_vartime(rho_fr, &e, 1), wj);
+      off = jac_add(off, jac_mul(jac_from_affine(pt_neg(g1_gen())), wj, 4));
+    }
+    bh_srs d_ic;
+    if ((s = srs_upload_affine(ctx, ic.data(), ni, &d_ic))) return s;
+    if ((s = g1(&d_ic, w, ni, &ic_l))) return s;
+    ic_l = jac_add(ic_l, off);
+  }
+  // the right-hand sides, over the storage
+  const uint32_t* cw = sc.coef[0].as<uint32_t>();
+  if ((s = g1(T, cw, m, &a_r))) return s;
+  if ((s = g1(T, cw + m * 8, m, &b1_r))) return s;
+  if ((s = g2(T2, cw + m * 8, m, &b2_r))) return s;
+  if ((s = g1(T, hw, 2 * m, &h_r))) return s;
+  for (int z = 0; z < 2; z++) {  // K(w), K(w_in) = <BT, c_A> + <AT, c_B> + <T, c_C>
+    const uint32_t* c = sc.coef[z].as<uint32_t>();
+    const bh_srs* base[3] = {BT, AT, T};
+    k[z] = jac_identity<Fp>();
+    for (int v = 0; v < 3; v++) {
+      Jac<Fp> part;
+      if ((s = g1(base[v], c + (size_t)v * m * 8, m, &part))) return s;
+      k[z] = jac_add(k[z], part);
+    }
+  }
+  const AffinePt<Fp> k_in = jac_to_affine(k[1]);
+  const AffinePt<Fp> k_aux = jac_to_affine(jac_add(k[0], jac_from_affine(pt_neg(k_in))));
+  g_pcheck_ms[1] = ms_since(t0);
+  // ---- bytes, point equalities, pairings
+  t0 = std::chrono::steady_clock::now();
+  if (!same_bytes(p->alpha_g1, st->p1[0])) mask |= BH_PARAMS_CHECK_ALPHA;
+  if (!same_bytes(p->beta_g1, st->p1[1]) || !same_bytes(p->beta_g2, st->p2[1])) mask |= BH_PARAMS_CHECK_BETA;
+  if (p->gamma_g2.infinity || p->delta_g2.infinity) mask |= BH_PARAMS_CHECK_DELTA;
+  if (!same_bytes(jac_to_affine(a_l), jac_to_affine(a_r))) mask |= BH_PARAMS_CHECK_A;
+  if (!same_bytes(jac_to_affine(b1_l), jac_to_affine(b1_r))) mask |= BH_PARAMS_CHECK_B_G1;
+  if (!same_bytes(jac_to_affine(b2_l), jac_to_affine(b2_r))) mask |= BH_PARAMS_CHECK_B_G2;
+  const AffinePt<Fp2> ng2 = pt_neg(g2_gen());
+  const std::vector<Equation> eq = {
+      {BH_PARAMS_CHECK_DELTA, {{p->delta_g1, ng2}, {g1_gen(), p->delta_g2}}},
+      {BH_PARAMS_CHECK_L, {{jac_to_affine(l_l), p->delta_g2}, {k_aux, ng2}}},
+      {BH_PARAMS_CHECK_IC, {{jac_to_affine(ic_l), p->gamma_g2}, {k_in, ng2}}},
+      {BH_PARAMS_CHECK_H, {{jac_to_affine(h_l), p->delta_g2}, {jac_to_affine(h_r), ng2}}}};
+  std::vector<char> bad(eq.size(), 0);  // every equation is evaluated: the mask is complete
+  ctx_pool(ctx).parallel_for((int)eq.size(), [&](int i) { bad[i] = !pairing_product_is_one(eq[i].pairs); });
+  for (size_t i = 0; i < eq.size(); i++)
+    if (bad[i]) mask |= eq[i].bit;
+  g_pcheck_ms[2] = ms_since(t0);
+  return done();
+}
+
+// wall time (ms) of this thread's last bh_params_check: the scalar side, the multiexps, the pairings
+void bh_params_last_check_ms(double out[3]) {
+  for (int i = 0; i < 3; i++) out[i] = g_pcheck_ms[i];
 }
 
 // wall time (ms) of the per-element Miller loops of this thread's last bh_mpc_common_verify, and

@@ -65,6 +65,17 @@ std::vector<AffinePt<Fp2>> crs_table_g2();
 template <class C>
 bh_status fixed_base_device(bh_ctx* ctx, const bh_srs& tab, const uint32_t* d_sc, size_t n, bh_srs* out);
 
+// r1cs.hip, for callers whose vectors are resident (params_check.hip); the caller holds ctx->mu.
+// r1cs_powers_device: d_out[i] = x^i, i < n, packed device Montgomery (k_r1cs_powers), on ctx->stream,
+// synchronised.  r1cs_eval_device: the QAP evaluation behind bh_r1cs_eval, u | v | w (3 (ni + na)
+// values) into d_y for the m values d_x, d_part max(nseg, 1) values of scratch; enqueued on st.
+// r1cs_rows_device: the row product behind bh_r1cs_witness, a | b | c = A z | B z | C z (3 m values,
+// the rows nc .. m zero) for z = [inputs, aux] (packed device Montgomery, < 2r); builds the handle's
+// row view on first use (under its lock), sizes *part as scratch, enqueues on st
+bh_status r1cs_powers_device(bh_ctx* ctx, const Fr& x, size_t n, uint32_t* d_out);
+hipError_t r1cs_eval_device(const bh_r1cs* r, const uint32_t* d_x, uint32_t* d_part, uint32_t* d_y, hipStream_t st);
+bh_status r1cs_rows_device(const bh_r1cs* r, const uint32_t* d_z, DevBuf* part, uint32_t* d_abc, hipStream_t st);
+
 // api.hip: the ifft (domain.rs:104-121) of 2^L packed device-Montgomery Fr resident in d_a, natural
 // order in and out, d_tmp the same size; enqueued on ctx->stream (caller holds ctx->mu)
 bh_status device_ifft(bh_ctx* ctx, Domain* D, uint32_t* d_a, uint32_t* d_tmp);

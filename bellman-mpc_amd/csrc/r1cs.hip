@@ -665,7 +665,51 @@ bh_status row_view(const bh_r1cs* r, hipStream_t st) {
   return BH_OK;
 }
 
+// a | b | c = the rows' sums of the ready row view against z (n packed device-Montgomery Fr), d_part
+// rv.nseg values of scratch: every one of the 3 m rows is written, the empty ones (nc .. m of each
+// matrix) with zero.  Enqueued on st; the caller holds r->rv.mu
+hipError_t rows_product(const bh_r1cs* r, const uint32_t* d_z, uint32_t* d_part, uint32_t* d_abc, hipStream_t st) {
+  const bh_r1cs::RowView& rv = r->rv;
+  if (rv.nseg)
+    hipLaunchKernelGGL(k_r1cs_row_segments, dim3(nb(rv.nseg, 256)), dim3(256), 0, st, r->coeff.as<uint32_t>(),
+                       rv.term.as<uint32_t>(), rv.var.as<uint32_t>(), rv.seg.as<uint32_t>(), (uint32_t)rv.nseg, d_z,
+                       d_part);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return sum_partials(rv.rowseg.as<uint32_t>(), rv.nrows, rv.longrows.as<uint32_t>(), rv.nlong, d_part, d_abc, st);
+}
+
 }  // namespace
+
+namespace bh {
+
+bh_status r1cs_powers_device(bh_ctx* ctx, const Fr& x, size_t n, uint32_t* d_out) {
+  if (!n) return BH_OK;
+  int L = 0;
+  while (((size_t)1 << L) < n) L++;
+  const int lo_bits = (L + 1) / 2;
+  DevBuf lo, hi;
+  if (bh_status s = upload_split_table(ctx, lo, hi, x, Fr::one(), L, lo_bits)) return s;
+  hipLaunchKernelGGL(k_r1cs_powers, dim3(nb(n, 256)), dim3(256), 0, ctx->stream, d_out, (uint32_t)n,
+                     lo.as<uint32_t>(), hi.as<uint32_t>(), lo_bits);
+  BH_TRY_HIP(hipGetLastError());
+  BH_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the tables are freed on return
+  return BH_OK;
+}
+
+hipError_t r1cs_eval_device(const bh_r1cs* r, const uint32_t* d_x, uint32_t* d_part, uint32_t* d_y, hipStream_t st) {
+  return qap_eval(r, d_x, d_part, d_y, st);
+}
+
+bh_status r1cs_rows_device(const bh_r1cs* r, const uint32_t* d_z, DevBuf* part, uint32_t* d_abc, hipStream_t st) {
+  std::lock_guard<std::mutex> rlk(r->rv.mu);
+  if (bh_status s = row_view(r, st)) return s;
+  BH_TRY_HIP(part->alloc(std::max<size_t>(r->rv.nseg, 1) * 32));
+  BH_TRY_HIP(rows_product(r, d_z, part->as<uint32_t>(), d_abc, st));
+  return BH_OK;
+}
+
+}  // namespace bh
 
 extern "C" {
 
@@ -712,15 +756,9 @@ bh_status bh_r1cs_witness(bh_ctx* ctx, const bh_r1cs* r, const uint64_t* input_a
     BH_TRY_HIP(hipGetLastError());
     BH_TRY_HIP(scalars_prepare(w->aux.as<uint32_t>(), w->aux.as<uint32_t>(), na, 1, 0, st));
   }
-  // a | b | c = the rows' sums, straight into the witness: every one of the 3 m rows is written,
-  // the empty ones (nc .. m of each matrix) with zero
+  // a | b | c = the rows' sums, straight into the witness
   uint32_t* abc = w->abc.as<uint32_t>();
-  if (rv.nseg)
-    hipLaunchKernelGGL(k_r1cs_row_segments, dim3(nb(rv.nseg, 256)), dim3(256), 0, st, r->coeff.as<uint32_t>(),
-                       rv.term.as<uint32_t>(), rv.var.as<uint32_t>(), rv.seg.as<uint32_t>(), (uint32_t)rv.nseg, d_z,
-                       d_part);
-  BH_TRY_HIP(hipGetLastError());
-  BH_TRY_HIP(sum_partials(rv.rowseg.as<uint32_t>(), rv.nrows, rv.longrows.as<uint32_t>(), rv.nlong, d_part, abc, st));
+  BH_TRY_HIP(rows_product(r, d_z, d_part, abc, st));
   uint32_t first = 0xffffffffu;
   if (first_unsatisfied) {
     uint32_t* d_first = rv.words.as<uint32_t>() + 1;

@@ -22,6 +22,7 @@
 #include "group_fft.h"
 #include "gt.h"
 #include "pairing_dev.h"
+#include "params_check.h"
 #include "point_codec.h"
 #include "proofs_dev.h"
 #include "r1cs.h"
@@ -95,6 +96,7 @@ bh_status scratch_report(bh_ctx* ctx, uint64_t out[10], std::string* worst) {
   r1cs_kernels(ks);
   varbase_kernels(ks);
   group_fft_kernels(ks);
+  params_check_kernels(ks);
   pairing_kernels(ks);
   proofs_kernels(ks);
   point_codec_kernels(ks);

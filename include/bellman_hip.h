@@ -30,6 +30,8 @@
  *   bh_mpc_parameters      generate_parameters_mpc        groth16/generator.rs:163-237
  *   bh_mpc_common_check / _verify_structure
  *                          the power-sequence check of a round-one storage (not in the reference)
+ *   bh_params_check        Parameters against a circuit and such a storage (not in the reference;
+ *                          the queries it audits: groth16/generator.rs:520-572, 614-633)
  *
  * Conventions
  *   - Plain pointers and sizes only; the caller owns every host buffer and the
@@ -756,6 +758,74 @@ bh_status bh_mpc_parameters(bh_ctx* ctx, const bh_mpc_common* round1, const bh_m
 /* wall time (ms) of the parts of this thread's last bh_mpc_common_matrix: [0] the six inverse
  * transforms, [1] the matrix product, [2] the h basis (every part synchronises) */
 void bh_mpc_last_matrix_ms(double out[3]);
+
+/* ---- Parameters checked against a circuit and a round-one storage (no counterpart in the
+ * reference).  bh_params_load(checked = 1) shows that the points of received
+ * Parameters are in the subgroup, nothing more; the only other way to know that they belong to THIS
+ * circuit and THIS power sequence is to rebuild them (bh_mpc_common_matrix and every round-two
+ * contribution) and compare bytes.  With tau, alpha, beta the scalars of a well-formed storage S
+ * (above), n = inputs + aux variables and m the domain size of r, Parameters P are VALID FOR (r, S)
+ * iff gamma, delta != 0 exist such that P is byte for byte what bh_generate_parameters returns for
+ * r, alpha, beta, gamma, delta, tau (generator.rs:520-572, 614-633) -- which is also what
+ * bh_mpc_parameters returns after any round two.
+ *   bh_params_check   PRECONDITIONS: storage is well formed -- the initial one, or one accepted by
+ *                     bh_mpc_common_check / bh_mpc_common_verify_structure; p was loaded checked or
+ *                     made by the library.  rho, sigma: TWO canonical scalars the caller draws
+ *                     independently at random.  BH_ERR_INVALID_ARGUMENT: a null handle or a handle on
+ *                     another device; rho or sigma zero or >= r; bh_mpc_common_len(storage) < 2m;
+ *                     m < 2.  With x_i = sigma^i, i < m, and u, v, w = bh_r1cs_eval at x, column j of
+ *                     A is PRESENT iff u_j != 0 and column j of B iff v_j != 0 (a column whose terms
+ *                     cancel has u_j = 0 for every sigma; the generator filters it too).  The
+ *                     weights are w_j = rho^j over [inputs, aux]; w_in = w on the inputs and zero
+ *                     elsewhere, w_aux = w - w_in, w^A / w^B = w compacted to the present columns of
+ *                     A / B with the order kept.  For a matrix M and weights z, c_M(z) is the inverse
+ *                     NTT (size m, with the 1/m) of the row vector M z, the appended input rows
+ *                     included: bh_r1cs_witness's a, b, c for the assignment z, so that
+ *                     sum_k c_M(z)_k tau^k = sum_j z_j M_j(tau).  T, AT, BT, T2 are the storage's
+ *                     tau_g1, alpha_mul_tau_g1, beta_mul_tau_g1, tau_g2; <V, s> is a multiexp;
+ *                     K(z) = <BT, c_A(z)> + <AT, c_B(z)> + <T, c_C(z)> over the first m elements.
+ *                     Bit k of *failed (may be NULL) is set iff equation k fails, *valid = (mask == 0):
+ *                       BH_PARAMS_CHECK_SIZES  ic = inputs, l = aux, h = m - 1, a = the present columns
+ *                                              of A, b_g1 = b_g2 = those of B (if not, this bit alone
+ *                                              is set and nothing else runs)
+ *                       BH_PARAMS_CHECK_ALPHA  vk.alpha_g1 == the storage's alpha_g1 (bytes)
+ *                       BH_PARAMS_CHECK_BETA   vk.beta_g1, vk.beta_g2 == the storage's (bytes)
+ *                       BH_PARAMS_CHECK_DELTA  e(delta_g1, G2) == e(G1, delta_g2), and neither
+ *                                              gamma_g2 nor delta_g2 is the identity
+ *                       BH_PARAMS_CHECK_A      <a, w^A> == <T, c_A(w)>  (equal points, no pairing)
+ *                       BH_PARAMS_CHECK_B_G1   <b_g1, w^B> == <T, c_B(w)>
+ *                       BH_PARAMS_CHECK_B_G2   <b_g2, w^B> == <T2, c_B(w)>
+ *                       BH_PARAMS_CHECK_L      e(<l, w_aux>, delta_g2) == e(K(w_aux), G2),
+ *                                              K(w_aux) computed as K(w) - K(w_in)
+ *                       BH_PARAMS_CHECK_IC     e(<ic, w_in>, gamma_g2) == e(K(w_in), G2)
+ *                       BH_PARAMS_CHECK_H      e(sum_{i < m-1} rho^i h_i, delta_g2)
+ *                                                == e(sum_{i < m-1} rho^i (T[i + m] - T[i]), G2),
+ *                                              the right side one multiexp of length 2m, signed weights
+ *                     Every equation is evaluated (no early exit); a sum that is the identity pairs
+ *                     to one.  Valid Parameters pass unless sigma is a root of a present column's
+ *                     polynomial (probability below 2 n m / r; SIZES is then set); invalid ones pass
+ *                     an equation they violate with probability below 3 n m / r over (rho, sigma),
+ *                     below 2^-190 for every size bh_r1cs_create accepts.  Cost: two row products, six scalar inverse
+ *                     NTTs of size m, sixteen multiexps (fourteen in G1, two in G2: nine of
+ *                     length m, one of 2m, six over the Parameters' own vectors) and four
+ *                     pairing equations on the host's pool; no group FFT, and no scalar vector
+ *                     crosses the host link.
+ *   bh_params_last_check_ms   wall time (ms) of this thread's last bh_params_check: [0] the scalar
+ *                     side (powers, evaluation, row products, NTTs), [1] the multiexps, [2] the
+ *                     byte comparisons and pairings */
+#define BH_PARAMS_CHECK_SIZES (1u << 0)
+#define BH_PARAMS_CHECK_ALPHA (1u << 1)
+#define BH_PARAMS_CHECK_BETA (1u << 2)
+#define BH_PARAMS_CHECK_DELTA (1u << 3)
+#define BH_PARAMS_CHECK_A (1u << 4)
+#define BH_PARAMS_CHECK_B_G1 (1u << 5)
+#define BH_PARAMS_CHECK_B_G2 (1u << 6)
+#define BH_PARAMS_CHECK_L (1u << 7)
+#define BH_PARAMS_CHECK_IC (1u << 8)
+#define BH_PARAMS_CHECK_H (1u << 9)
+bh_status bh_params_check(bh_ctx* ctx, const bh_params* p, const bh_r1cs* r, const bh_mpc_common* storage,
+                          const uint64_t rho[4], const uint64_t sigma[4], int* valid, uint32_t* failed);
+void bh_params_last_check_ms(double out[3]);
 
 /* wall time (ms) the per-element Miller loops took in this thread's last bh_mpc_common_verify, on
  * whichever path ran them: the device product below (the default), or the host's pool threads
