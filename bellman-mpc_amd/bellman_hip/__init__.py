@@ -183,6 +183,9 @@ def _load():
         "bh_srs_read": (I, [P, S, S, P]),
         "bh_srs_upload_compressed": (I, [P, I, P, S, I, P]),
         "bh_srs_read_compressed": (I, [P, S, S, P]),
+        "bh_srs_last_codec_device": (I, []),
+        "bh_params_load_compressed": (I, [P, P, S, I, P]),
+        "bh_params_write_compressed": (I, [P, P, S, P]),
         "bh_mpc_common_matrix": (I, [P, P, P, P]),
         "bh_mpc_matrix_vector": (I, [P, I, P]),
         "bh_mpc_matrix_free": (I, [P]),
@@ -268,7 +271,8 @@ EXPORTED_SYMBOLS = [
     "bh_mpc_parameters", "bh_mpc_last_matrix_ms", "bh_final_exponentiation_batch", "bh_verify_each_device",
     "bh_mpc_common_check", "bh_mpc_common_verify_structure", "bh_mpc_last_check_ms",
     "bh_params_check", "bh_params_last_check_ms",
-    "bh_srs_upload_compressed", "bh_srs_read_compressed",
+    "bh_srs_upload_compressed", "bh_srs_read_compressed", "bh_srs_last_codec_device",
+    "bh_params_load_compressed", "bh_params_write_compressed",
     "bh_gt_pairing", "bh_gt_from_miller", "bh_gt_upload", "bh_gt_read", "bh_gt_len", "bh_gt_free", "bh_gt_add",
     "bh_gt_neg", "bh_gt_mul_each", "bh_gt_sum", "bh_gt_multiexp",
 ] + [f"bh_mpc_{kind}{who}_{op}" for kind in ("common", "uncommon") for who in ("", "_contrib")
@@ -880,10 +884,13 @@ class Parameters:
         self.ctx, self.h = ctx, handle
 
     @classmethod
-    def read(cls, ctx, data: bytes, checked=True):
-        buf = np.frombuffer(data, dtype=np.uint8)
+    def read(cls, ctx, data: bytes, checked=True, compressed=False):
+        """Parameters::read; compressed: the same layout with every point compressed
+        (bh_params_load_compressed)."""
+        buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
         h = ctypes.c_void_p()
-        _check(_lib.bh_params_load(ctx.h, _ptr(buf), len(data), int(checked), ctypes.byref(h)), "Parameters::read")
+        load = _lib.bh_params_load_compressed if compressed else _lib.bh_params_load
+        _check(load(ctx.h, _ptr(buf), len(data), int(checked), ctypes.byref(h)), "Parameters::read")
         return cls(ctx, h)
 
     @classmethod
@@ -908,11 +915,14 @@ class Parameters:
         _check(_lib.bh_params_sizes(self.h, out))
         return dict(zip(["h", "l", "a", "b_g1", "b_g2", "ic"], list(out)))
 
-    def write(self):
+    def write(self, compressed=False):
+        """Parameters::write; compressed: the same layout with every point compressed
+        (bh_params_write_compressed)."""
+        write = _lib.bh_params_write_compressed if compressed else _lib.bh_params_write
         n = ctypes.c_size_t()
-        _check(_lib.bh_params_write(self.h, None, 0, ctypes.byref(n)))
+        _check(write(self.h, None, 0, ctypes.byref(n)))
         out = np.zeros(n.value, dtype=np.uint8)
-        _check(_lib.bh_params_write(self.h, _ptr(out), n.value, ctypes.byref(n)))
+        _check(write(self.h, _ptr(out), n.value, ctypes.byref(n)))
         return out.tobytes()
 
     def vector(self, which):

@@ -13,6 +13,7 @@
 
 #include "api_internal.h"
 #include "dist_h.h"
+#include "point_codec.h"
 
 using namespace bh;
 
@@ -184,9 +185,10 @@ bh_status srs_upload_affine(bh_ctx* ctx, const AffinePt<T>* pts, size_t n, bh_sr
 template bh_status srs_upload_affine<Fp>(bh_ctx*, const AffinePt<Fp>*, size_t, bh_srs*);
 template bh_status srs_upload_affine<Fp2>(bh_ctx*, const AffinePt<Fp2>*, size_t, bh_srs*);
 
-// parse n uncompressed encodings; returns BH_ERR_INVALID_ENCODING / BH_ERR_NOT_ON_CURVE
-bh_status srs_from_bytes(bh_ctx* ctx, int group, const uint8_t* bytes, size_t n, int checked,
-                                bool reject_identity, bh_srs* out) {
+// parse n uncompressed encodings on the host, one point after the other (BH_POINT_CODEC_HOST=1);
+// returns BH_ERR_INVALID_ENCODING / BH_ERR_NOT_ON_CURVE
+static bh_status srs_from_bytes_host(bh_ctx* ctx, int group, const uint8_t* bytes, size_t n, int checked,
+                                     bool reject_identity, bh_srs* out) {
   return with_group(group, [&](auto g) -> bh_status {
     using G = decltype(g);
     using T = typename G::Field;
@@ -221,6 +223,42 @@ bh_status srs_from_bytes(bh_ctx* ctx, int group, const uint8_t* bytes, size_t n,
     }
     return srs_convert<G>(ctx, w, checked, out);
   });
+}
+
+// n uncompressed encodings -> out: decoded on the device in place (point_codec.hip), or by the host
+// loop above under BH_POINT_CODEC_HOST=1; the same vector and the same status either way
+bh_status srs_from_bytes(bh_ctx* ctx, int group, const uint8_t* bytes, size_t n, int checked, bool reject_identity,
+                         bh_srs* out) {
+  const bool host = point_codec_host();
+  point_codec_note(!host);
+  return host ? srs_from_bytes_host(ctx, group, bytes, n, checked, reject_identity, out)
+              : srs_from_wire(ctx, group, bytes, n, checked, reject_identity, out);
+}
+
+// points first .. first + n of v as uncompressed bytes on the host, one point after the other
+static bh_status srs_read_host(const bh_srs* srs, size_t first, size_t n, uint8_t* out) {
+  return with_group(srs->group, [&](auto g) -> bh_status {
+    using G = decltype(g);
+    std::vector<uint32_t> w(n * G::WORDS);
+    BH_TRY_HIP(hipMemcpy(w.data(), srs->pts.as<uint32_t>() + first * G::WORDS, w.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<bool> inf(n, false);
+    for (size_t i : srs->identity_idx)
+      if (i >= first && i - first < n) inf[i - first] = true;
+    for (size_t i = 0; i < n; i++) {
+      typename G::Affine a = G::from_dev_words(&w[i * G::WORDS]);
+      a.infinity = inf[i];
+      to_uncompressed(a, out + i * G::WIRE);
+    }
+    return BH_OK;
+  });
+}
+
+bh_status srs_read_bytes(bh_ctx* ctx, const bh_srs* srs, size_t first, size_t n, uint8_t* out) {
+  if (first > srs->n || n > srs->n - first) return BH_ERR_INVALID_ARGUMENT;
+  const bool host = point_codec_host();
+  point_codec_note(!host);
+  if (!n) return BH_OK;
+  return host ? srs_read_host(srs, first, n, out) : srs_to_wire(ctx, srs, first, n, out);
 }
 
 template <class G>
@@ -934,20 +972,11 @@ bh_status bh_srs_get(const bh_srs* srs, size_t i, uint8_t* out) {
 bh_status bh_srs_read(const bh_srs* srs, size_t first, size_t n, uint8_t* out) {
   if (!srs || (n && !out) || first > srs->n || n > srs->n - first) return BH_ERR_INVALID_ARGUMENT;
   if (!n) return BH_OK;
-  return with_group(srs->group, [&](auto g) -> bh_status {
-    using G = decltype(g);
-    std::vector<uint32_t> w(n * G::WORDS);
-    BH_TRY_HIP(hipMemcpy(w.data(), srs->pts.as<uint32_t>() + first * G::WORDS, w.size() * 4, hipMemcpyDeviceToHost));
-    std::vector<bool> inf(n, false);
-    for (size_t i : srs->identity_idx)
-      if (i >= first && i - first < n) inf[i - first] = true;
-    for (size_t i = 0; i < n; i++) {
-      typename G::Affine a = G::from_dev_words(&w[i * G::WORDS]);
-      a.infinity = inf[i];
-      to_uncompressed(a, out + i * G::WIRE);
-    }
-    return BH_OK;
-  });
+  bh_ctx* ctx = srs->ctx;
+  if (!ctx) return BH_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  BH_TRY_HIP(hipSetDevice(ctx->device));
+  return srs_read_bytes(ctx, srs, first, n, out);
 }
 
 // ---------------------------------------------------------------- multiexp

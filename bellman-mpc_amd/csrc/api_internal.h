@@ -514,6 +514,10 @@ bh_status run_h_vector(bh_ctx* ctx, Domain* D, uint32_t* d_abc, hipStream_t st, 
 bh_status run_h_final(bh_ctx* ctx, Domain* D, uint32_t* d_abc, hipStream_t st, uint32_t* hout);
 bh_status srs_from_bytes(bh_ctx* ctx, int group, const uint8_t* bytes, size_t n, int checked, bool reject_identity,
                          bh_srs* out);
+// points first .. first + n of a device vector as uncompressed bytes (bh_srs_read without the lock:
+// the caller holds ctx->mu and has set the device); on the device codec, or the host loop under
+// BH_POINT_CODEC_HOST=1
+bh_status srs_read_bytes(bh_ctx* ctx, const bh_srs* srs, size_t first, size_t n, uint8_t* out);
 // api.hip's k_subgroup_check over n device-form points (all-zero records, the identity, are
 // skipped), enqueued on ctx->stream: the zeroed device word *d_bad becomes non-zero when a point is
 // outside the subgroup

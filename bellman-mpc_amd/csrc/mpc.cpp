@@ -271,17 +271,10 @@ void put(std::vector<uint8_t>& v, const AffinePt<T>& p, bool compressed) {
   v.insert(v.end(), b, b + wire_bytes(HostOfField<T>::ID, compressed));
 }
 bh_status put_vec(std::vector<uint8_t>& v, bh_ctx* ctx, const bh_srs* s, bool compressed) {
-  if (compressed) {
-    const size_t at = v.size();
-    v.resize(at + s->n * compressed_bytes(s->group));
-    return srs_to_compressed(ctx, s, 0, s->n, v.data() + at);
-  }
-  return with_group(s->group, [&](auto g) {
-    std::vector<typename decltype(g)::Affine> h;
-    const bh_status st = download(s, &h);
-    for (const auto& p : h) put(v, p, false);
-    return st;
-  });
+  const size_t at = v.size();
+  v.resize(at + s->n * wire_bytes(s->group, compressed));
+  if (compressed) return srs_to_compressed(ctx, s, 0, s->n, v.data() + at);
+  return srs_read_bytes(ctx, s, 0, s->n, v.data() + at);  // the codec, or the host loop under its knob
 }
 
 struct Reader {
@@ -325,21 +318,24 @@ struct Reader {
     o += n * pair;
     for (int k = 0; k < 4; k++) dst[k]->reset(new bh_srs());
     bh_status s;
-    if (compressed) {  // the interleaved list goes to the device as it is; the codec reads it strided
+    if (compressed || !point_codec_host()) {
+      // the interleaved list goes to the device as it is; the codec reads it strided
+      if (!compressed) point_codec_note(true);
       DevBuf raw;
       BH_TRY_HIP(raw.alloc(std::max<size_t>(n * pair, 16)));
       if (n) BH_TRY_HIP(hipMemcpyAsync(raw.p, list, n * pair, hipMemcpyHostToDevice, ctx->stream));
       size_t off = 0;
       for (int k = 0; k < 4; k++) {
         // each call returns synchronised, so raw outlives every read of it
-        if ((s = points_decompress_device(ctx, k & 1 ? BH_G2 : BH_G1, raw.as<uint8_t>(), pair, off, n, checked, true,
-                                          dst[k]->get())))
-          return s;
+        const int group = k & 1 ? BH_G2 : BH_G1;
+        s = compressed ? points_decompress_device(ctx, group, raw.as<uint8_t>(), pair, off, n, checked, true, dst[k]->get())
+                       : points_from_wire_device(ctx, group, raw.as<uint8_t>(), pair, off, n, checked, true, dst[k]->get());
+        if (s) return s;
         off += w[k];
       }
       return BH_OK;
     }
-    // de-interleave the list into its four vectors
+    // BH_POINT_CODEC_HOST=1: de-interleave the list into its four vectors on the host
     std::vector<uint8_t> col[4];
     for (int k = 0; k < 4; k++) col[k].resize(n * w[k]);
     for (size_t i = 0; i < n; i++) {
@@ -413,10 +409,11 @@ bh_status contrib_write(const MpcContrib* c, bool common, bool compressed, std::
     put(v, p.m2, compressed);
   }
   for (int j = 0; j < 3; j++) {
-    if (compressed) {  // the four vectors coded into one interleaved device list, one copy back
+    if (compressed || !point_codec_host()) {  // the four vectors coded into one interleaved device list, one copy back
+      if (!compressed) point_codec_note(true);
       const bh_srs* col[4] = {c->res[2 * j].get(), c->res[2 * j + 1].get(), c->mine[2 * j].get(),
                               c->mine[2 * j + 1].get()};
-      const size_t n = col[0]->n, pair = 2 * (compressed_bytes(BH_G1) + compressed_bytes(BH_G2));
+      const size_t n = col[0]->n, pair = 2 * (wire_bytes(BH_G1, compressed) + wire_bytes(BH_G2, compressed));
       put_u32(v, n);
       const size_t at = v.size();
       v.resize(at + n * pair);
@@ -426,18 +423,22 @@ bh_status contrib_write(const MpcContrib* c, bool common, bool compressed, std::
       size_t off = 0;
       for (int k = 0; k < 4; k++) {
         if (col[k]->n != n) return BH_ERR_INVALID_ARGUMENT;
-        if (bh_status s = points_compress_device(c->ctx, col[k], 0, n, d.as<uint8_t>(), pair, off)) return s;
-        off += compressed_bytes(col[k]->group);
+        if (bh_status s = compressed ? points_compress_device(c->ctx, col[k], 0, n, d.as<uint8_t>(), pair, off)
+                                     : points_to_wire_device(c->ctx, col[k], 0, n, d.as<uint8_t>(), pair, off))
+          return s;
+        off += wire_bytes(col[k]->group, compressed);
       }
       BH_TRY_HIP(hipMemcpyAsync(v.data() + at, d.p, n * pair, hipMemcpyDeviceToHost, c->ctx->stream));
       BH_TRY_HIP(hipStreamSynchronize(c->ctx->stream));  // d is freed at the end of the round
       off = 0;
       for (int k = 0; k < 4; k++) {
-        points_compress_patch(col[k], 0, n, v.data() + at, pair, off);
-        off += compressed_bytes(col[k]->group);
+        if (compressed) points_compress_patch(col[k], 0, n, v.data() + at, pair, off);
+        else points_wire_patch(col[k], 0, n, v.data() + at, pair, off);
+        off += wire_bytes(col[k]->group, compressed);
       }
       continue;
     }
+    point_codec_note(false);
     std::vector<AffinePt<Fp>> r1, m1;
     std::vector<AffinePt<Fp2>> r2, m2;
     bh_status s;

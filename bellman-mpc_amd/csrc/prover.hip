@@ -12,6 +12,8 @@
 #include "api_internal.h"
 #include "crs.h"
 #include "dist_h.h"
+#include "pairing.h"
+#include "point_codec.h"
 #include "proof_schedule.h"
 
 using namespace bh;
@@ -35,23 +37,41 @@ struct Reader {
   }
 };
 
+// Parameters exist in two encodings with one layout: Parameters::write's (every point uncompressed,
+// groth16/mod.rs:260-400) and the same with every point compressed.  Vectors go through the device
+// codec (point_codec.hip), the VerifyingKey's few points through the host's coders.
+size_t point_bytes(int group, bool compressed) {
+  return compressed ? compressed_bytes(group) : uncompressed_bytes(group);
+}
+
 // VerifyingKey::read uses from_uncompressed (checked), groth16/mod.rs:161-222
 template <class T>
-bh_status read_vk_point(Reader& r, AffinePt<T>* out, bool reject_identity) {
+bh_status read_vk_point(Reader& r, AffinePt<T>* out, bool reject_identity, bool compressed = false) {
   const uint8_t* b;
-  if (!r.take(HostOfField<T>::WIRE, &b)) return BH_ERR_INVALID_ENCODING;
-  if (from_uncompressed(b, out, true, true) != 0) return BH_ERR_INVALID_ENCODING;
+  if (!r.take(point_bytes(HostOfField<T>::ID, compressed), &b)) return BH_ERR_INVALID_ENCODING;
+  if (compressed) {
+    const size_t pb = point_bytes(HostOfField<T>::ID, true);
+    if ((b[0] >> 5) == 0x6) {  // the infinity encoding: c0 00 ... 00, accepted where from_uncompressed's is
+      for (size_t k = 0; k < pb; k++)
+        if ((k == 0 ? (b[0] & 0x1F) : b[k]) != 0) return BH_ERR_INVALID_ENCODING;
+      out->infinity = true; out->x = tzero<T>(); out->y = tzero<T>();
+    } else if (point_from_compressed(b, out, true) != BH_OK) {  // flags, range, squareness, subgroup
+      return BH_ERR_INVALID_ENCODING;
+    }
+  } else if (from_uncompressed(b, out, true, true) != 0) {
+    return BH_ERR_INVALID_ENCODING;
+  }
   if (reject_identity && out->infinity) return BH_ERR_INVALID_ENCODING;
   return BH_OK;
 }
 
-bh_status read_vec(bh_ctx* ctx, Reader& r, int group, int checked, bh_srs* out) {
+bh_status read_vec(bh_ctx* ctx, Reader& r, int group, int checked, bh_srs* out, bool compressed = false) {
   uint32_t len;
   if (!r.u32be(&len)) return BH_ERR_INVALID_ENCODING;
-  const size_t pb = with_group(group, [](auto g) { return decltype(g)::WIRE; });
   const uint8_t* b;
-  if (!r.take((size_t)len * pb, &b)) return BH_ERR_INVALID_ENCODING;
+  if (!r.take((size_t)len * point_bytes(group, compressed), &b)) return BH_ERR_INVALID_ENCODING;
   // Parameters::read rejects points at infinity in every vector (mod.rs:309-318)
+  if (compressed) return srs_from_compressed(ctx, group, b, len, checked, true, out);
   bh_status s = srs_from_bytes(ctx, group, b, len, checked, true, out);
   if (s == BH_ERR_NOT_ON_CURVE) return BH_ERR_INVALID_ENCODING;
   return s;
@@ -62,31 +82,87 @@ void put_u32be(std::vector<uint8_t>& out, size_t n) {
   out.push_back((uint8_t)(n >> 8)); out.push_back((uint8_t)n);
 }
 template <class T>
-void put_point(std::vector<uint8_t>& out, const AffinePt<T>& p) {
-  out.resize(out.size() + HostOfField<T>::WIRE);
-  to_uncompressed(p, &out[out.size() - HostOfField<T>::WIRE]);
+void put_point(std::vector<uint8_t>& out, const AffinePt<T>& p, bool compressed = false) {
+  const size_t pb = point_bytes(HostOfField<T>::ID, compressed);
+  out.resize(out.size() + pb);
+  if (compressed) to_compressed(p, &out[out.size() - pb]);
+  else to_uncompressed(p, &out[out.size() - pb]);
 }
 
-void write_vec(const bh_srs& v, std::vector<uint8_t>& out) {
-  put_u32be(out, v.n);
-  with_group(v.group, [&](auto g) {
-    using G = decltype(g);
-    std::vector<typename G::Affine> pts;
-    (void)download_points<G>(v, v.n, &pts);
-    for (const auto& p : pts) put_point(out, p);
-  });
+// one vector behind its u32-BE length, written at *at, which moves past it (the caller holds ctx->mu)
+bh_status write_vec(bh_ctx* ctx, const bh_srs& v, bool compressed, uint8_t** at) {
+  uint8_t* b = *at;
+  b[0] = (uint8_t)(v.n >> 24); b[1] = (uint8_t)(v.n >> 16); b[2] = (uint8_t)(v.n >> 8); b[3] = (uint8_t)v.n;
+  *at = b + 4 + v.n * point_bytes(v.group, compressed);
+  if (compressed) return srs_to_compressed(ctx, &v, 0, v.n, b + 4);
+  return srs_read_bytes(ctx, &v, 0, v.n, b + 4);
 }
 
 // VerifyingKey::write (groth16/mod.rs:139-159): the six points, then ic behind its u32-BE length
-void write_vk(const bh_params* p, std::vector<uint8_t>& v) {
-  put_point(v, p->alpha_g1);
-  put_point(v, p->beta_g1);
-  put_point(v, p->beta_g2);
-  put_point(v, p->gamma_g2);
-  put_point(v, p->delta_g1);
-  put_point(v, p->delta_g2);
+void write_vk(const bh_params* p, std::vector<uint8_t>& v, bool compressed = false) {
+  put_point(v, p->alpha_g1, compressed);
+  put_point(v, p->beta_g1, compressed);
+  put_point(v, p->beta_g2, compressed);
+  put_point(v, p->gamma_g2, compressed);
+  put_point(v, p->delta_g1, compressed);
+  put_point(v, p->delta_g2, compressed);
   put_u32be(v, p->ic.size());
-  for (const auto& ic : p->ic) put_point(v, ic);
+  for (const auto& ic : p->ic) put_point(v, ic, compressed);
+}
+
+// the size of either encoding, from the lengths alone
+size_t params_bytes(const bh_params* p, bool compressed) {
+  const size_t g1 = point_bytes(BH_G1, compressed), g2 = point_bytes(BH_G2, compressed);
+  return 3 * g1 + 3 * g2 + 4 + p->ic.size() * g1 + 5 * 4 + (p->h.n + p->l.n + p->a.n + p->b_g1.n) * g1 + p->b_g2.n * g2;
+}
+
+bh_status params_read(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bool compressed, bh_params** out) {
+  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  BH_TRY_HIP(hipSetDevice(ctx->device));
+  std::unique_ptr<bh_params> p(new bh_params());
+  p->ctx = ctx;
+  Reader r{bytes, bytes + len};
+  bh_status s;
+  if ((s = read_vk_point(r, &p->alpha_g1, false, compressed))) return s;
+  if ((s = read_vk_point(r, &p->beta_g1, false, compressed))) return s;
+  if ((s = read_vk_point(r, &p->beta_g2, false, compressed))) return s;
+  if ((s = read_vk_point(r, &p->gamma_g2, false, compressed))) return s;
+  if ((s = read_vk_point(r, &p->delta_g1, false, compressed))) return s;
+  if ((s = read_vk_point(r, &p->delta_g2, false, compressed))) return s;
+  uint32_t ic_len;
+  if (!r.u32be(&ic_len)) return BH_ERR_INVALID_ENCODING;
+  if ((size_t)(r.end - r.p) / point_bytes(BH_G1, compressed) < ic_len) return BH_ERR_INVALID_ENCODING;
+  p->ic.resize(ic_len);
+  for (uint32_t i = 0; i < ic_len; i++)
+    if ((s = read_vk_point(r, &p->ic[i], true, compressed))) return s;
+  if ((s = read_vec(ctx, r, BH_G1, checked, &p->h, compressed))) return s;
+  if ((s = read_vec(ctx, r, BH_G1, checked, &p->l, compressed))) return s;
+  if ((s = read_vec(ctx, r, BH_G1, checked, &p->a, compressed))) return s;
+  if ((s = read_vec(ctx, r, BH_G1, checked, &p->b_g1, compressed))) return s;
+  if ((s = read_vec(ctx, r, BH_G2, checked, &p->b_g2, compressed))) return s;
+  *out = p.release();
+  return BH_OK;
+}
+
+bh_status params_write(const bh_params* p, bool compressed, uint8_t* out, size_t cap, size_t* written) {
+  if (!p || !written) return BH_ERR_INVALID_ARGUMENT;
+  const size_t total = params_bytes(p, compressed);
+  *written = total;
+  if (!out) return BH_OK;  // size query: from the lengths alone
+  if (cap < total) return BH_ERR_INVALID_ARGUMENT;
+  bh_ctx* ctx = p->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  BH_TRY_HIP(hipSetDevice(ctx->device));
+  // the vectors' bytes go from the device straight into the caller's buffer
+  std::vector<uint8_t> vk;
+  write_vk(p, vk, compressed);
+  memcpy(out, vk.data(), vk.size());
+  uint8_t* at = out + vk.size();
+  bh_status s;
+  for (const bh_srs* vec : {&p->h, &p->l, &p->a, &p->b_g1, &p->b_g2})
+    if ((s = write_vec(ctx, *vec, compressed, &at))) return s;
+  return at == out + total ? BH_OK : BH_ERR_INVALID_ARGUMENT;
 }
 
 inline size_t popcount_words(const std::vector<uint64_t>& w, size_t nbits) {
@@ -263,31 +339,11 @@ bh_status witness_device(bh_ctx* ctx, bh_witness* w, const uint64_t* a, const ui
 extern "C" {
 
 bh_status bh_params_load(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_params** out) {
-  if (!ctx || !bytes || !out) return BH_ERR_INVALID_ARGUMENT;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  BH_TRY_HIP(hipSetDevice(ctx->device));
-  std::unique_ptr<bh_params> p(new bh_params());
-  p->ctx = ctx;
-  Reader r{bytes, bytes + len};
-  bh_status s;
-  if ((s = read_vk_point(r, &p->alpha_g1, false))) return s;
-  if ((s = read_vk_point(r, &p->beta_g1, false))) return s;
-  if ((s = read_vk_point(r, &p->beta_g2, false))) return s;
-  if ((s = read_vk_point(r, &p->gamma_g2, false))) return s;
-  if ((s = read_vk_point(r, &p->delta_g1, false))) return s;
-  if ((s = read_vk_point(r, &p->delta_g2, false))) return s;
-  uint32_t ic_len;
-  if (!r.u32be(&ic_len)) return BH_ERR_INVALID_ENCODING;
-  p->ic.resize(ic_len);
-  for (uint32_t i = 0; i < ic_len; i++)
-    if ((s = read_vk_point(r, &p->ic[i], true))) return s;
-  if ((s = read_vec(ctx, r, BH_G1, checked, &p->h))) return s;
-  if ((s = read_vec(ctx, r, BH_G1, checked, &p->l))) return s;
-  if ((s = read_vec(ctx, r, BH_G1, checked, &p->a))) return s;
-  if ((s = read_vec(ctx, r, BH_G1, checked, &p->b_g1))) return s;
-  if ((s = read_vec(ctx, r, BH_G2, checked, &p->b_g2))) return s;
-  *out = p.release();
-  return BH_OK;
+  return params_read(ctx, bytes, len, checked, false, out);
+}
+
+bh_status bh_params_load_compressed(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_params** out) {
+  return params_read(ctx, bytes, len, checked, true, out);
 }
 
 bh_status bh_params_free(bh_params* p) {
@@ -303,19 +359,11 @@ bh_status bh_params_sizes(const bh_params* p, size_t out[6]) {
 
 // Parameters::write (groth16/mod.rs:260-290)
 bh_status bh_params_write(const bh_params* p, uint8_t* out, size_t cap, size_t* written) {
-  if (!p || !written) return BH_ERR_INVALID_ARGUMENT;
-  std::vector<uint8_t> v;
-  write_vk(p, v);
-  write_vec(p->h, v);
-  write_vec(p->l, v);
-  write_vec(p->a, v);
-  write_vec(p->b_g1, v);
-  write_vec(p->b_g2, v);
-  *written = v.size();
-  if (!out) return BH_OK;  // size query
-  if (cap < v.size()) return BH_ERR_INVALID_ARGUMENT;
-  memcpy(out, v.data(), v.size());
-  return BH_OK;
+  return params_write(p, false, out, cap, written);
+}
+
+bh_status bh_params_write_compressed(const bh_params* p, uint8_t* out, size_t cap, size_t* written) {
+  return params_write(p, true, out, cap, written);
 }
 
 bh_status bh_witness_upload(bh_ctx* ctx, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t nc,

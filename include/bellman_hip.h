@@ -144,6 +144,14 @@ bh_status bh_srs_read(const bh_srs* srs, size_t first, size_t n, uint8_t* out);
 bh_status bh_srs_upload_compressed(bh_ctx* ctx, int group, const uint8_t* compressed_be, size_t n, int checked,
                                    bh_srs** out);
 bh_status bh_srs_read_compressed(const bh_srs* srs, size_t first, size_t n, uint8_t* out);
+/* The uncompressed vector paths (bh_srs_upload, bh_srs_read, the vectors of bh_params_load / _write
+ * and of the ceremony's uncompressed readers and writers) are coded on the device as well, one lane
+ * per point: they replace the per-point loops of G1Affine / G2Affine::
+ * from_uncompressed and into_uncompressed (groth16/mod.rs:260-400).  BH_POINT_CODEC_HOST=1 in the
+ * environment, read at each call, keeps the host loops instead (an A/B and diagnostic mode; bytes and
+ * statuses do not depend on it).  bh_srs_last_codec_device: 1 when the calling thread's last
+ * uncompressed vector upload or read ran on the device codec, 0 when it ran on the host loops. */
+int bh_srs_last_codec_device(void);
 
 /* ---- multiexp::multiexp.  density_words == NULL means FullDensity.  out: uncompressed
  * encoding of the projective result normalised to affine (96 B for G1, 192 B for G2). */
@@ -254,6 +262,16 @@ bh_status bh_compute_h(bh_ctx* ctx, const uint64_t* a, const uint64_t* b, const 
 /* ---- Parameters (groth16/mod.rs:224-477) */
 /* Parameters::read format (VerifyingKey::write then u32-BE length-prefixed h, l, a, b_g1, b_g2). */
 bh_status bh_params_load(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_params** out);
+/* The same layout with every point compressed (Parameters::read of groth16/mod.rs:292-400 with
+ * from_compressed in the place of from_uncompressed): the VerifyingKey's points 48 / 48 / 96 / 96 /
+ * 48 / 96 bytes, the u32-BE ic length and ic at 48 B each, then h, l, a, b_g1 (48 B per point) and
+ * b_g2 (96 B per point), each behind its u32-BE length.  The vectors are decoded on the device
+ * (bh_srs_upload_compressed's rules), the VerifyingKey's points on the host.  Statuses are
+ * bh_params_load's for the same defect: short input BH_ERR_INVALID_ENCODING; the identity refused in
+ * ic and in every vector; the VerifyingKey's points always fully checked; checked adds the subgroup
+ * test on the vectors (BH_ERR_NOT_IN_SUBGROUP).  The handle equals the one bh_params_load builds
+ * from the same points, word for word. */
+bh_status bh_params_load_compressed(bh_ctx* ctx, const uint8_t* bytes, size_t len, int checked, bh_params** out);
 bh_status bh_params_free(bh_params* p);
 /* sizes: [h, l, a, b_g1, b_g2, ic] */
 bh_status bh_params_sizes(const bh_params* p, size_t out[6]);
@@ -950,8 +968,12 @@ bh_status bh_verify_each_device(bh_ctx* ctx, const uint8_t* vk, size_t vk_len, c
 bh_status bh_proofs_decode(bh_ctx* ctx, const uint8_t* proofs, size_t k, uint32_t* status, bh_srs** a, bh_srs** b,
                            bh_srs** c);
 
-/* Parameters::write of device-resident params (for parity tests; host copy). */
+/* Parameters::write of device-resident params (groth16/mod.rs:260-290); the vectors are encoded on
+ * the device.  out == NULL: *written = the size, from the lengths alone. */
 bh_status bh_params_write(const bh_params* p, uint8_t* out, size_t cap, size_t* written);
+/* The same layout with every point compressed (Parameters::write with into_compressed in the place
+ * of into_uncompressed, groth16/mod.rs:260-290): what bh_params_load_compressed reads. */
+bh_status bh_params_write_compressed(const bh_params* p, uint8_t* out, size_t cap, size_t* written);
 
 /* ---- profile of the last bh_prove_witness[_partial] (device events):
  * [0] host wall ms, [1] H pipeline ms, [2] G1 accumulation ms (sum over launches),

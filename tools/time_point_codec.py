@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Timings of the compressed point codec against the uncompressed paths.
+"""Timings of the point codecs: the compressed one against the uncompressed paths (DESIGN.md section
+17), and, run once on this tree and once on a build of the parent commit (--package), the
+uncompressed paths on the device codec against the parent's host loops (section 20).
 
 For each 2^log_len and each group, on the vector a x^i G (bh_srs_mul_powers of the generators), the
 two variants alternating in one process, medians of --reps runs after one warm-up of each:
@@ -11,9 +13,17 @@ and, at 2^--mpc-log-len, on the storage after one contribution,
 
   * bh_mpc_common_write / bh_mpc_common_read(checked=0)  against the compressed pair.
 
+and, on the Parameters of the MiMC chain with 2^--params-log-len constraints (bh_chain_params),
+
+  * bh_params_load(checked=0), bh_params_write, and where the library has them
+    bh_params_load_compressed(checked=0), bh_params_write_compressed.
+
 Every call synchronises, so host wall time is the device time plus the call's host work, copies and
 allocations.  The bytes each call moves between host and device are reported alongside.
-usage: time_point_codec.py [--log-len 16 20] [--mpc-log-len 16] [--reps 5]"""
+--package DIR imports bellman_hip from DIR (another build's bellman-mpc_amd directory) instead of
+this tree's.
+usage: time_point_codec.py [--log-len 16 20] [--mpc-log-len 16] [--params-log-len 16 20] [--reps 5]
+                           [--package DIR]"""
 import argparse
 import ctypes
 import json
@@ -25,7 +35,6 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "bellman-mpc_amd"))
 sys.path.insert(0, ROOT)
 
 
@@ -57,8 +66,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-len", type=int, nargs="+", default=[16, 20])
     ap.add_argument("--mpc-log-len", type=int, default=16)
+    ap.add_argument("--params-log-len", type=int, nargs="*", default=[16, 20])
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--package", default=os.path.join(ROOT, "bellman-mpc_amd"))
     args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.package))
     import bellman_hip as bh
     lib = bh.lib()
     ctx = bh.Context(0)
@@ -142,6 +154,44 @@ def main():
         bytes(bufs[False])
     print(json.dumps(rec), flush=True)
     del st
+
+    for log_len in args.params_log_len:
+        params = bh.Parameters.chain(ctx, (1 << (log_len - 1)) - 1)
+        rec = {"constraints": 1 << log_len, "what": "bh_params", "sizes": params.sizes()}
+        forms = [("", lib.bh_params_load, lib.bh_params_write)]
+        if hasattr(lib, "bh_params_write_compressed"):
+            forms.append(("_compressed", lib.bh_params_load_compressed, lib.bh_params_write_compressed))
+        for suffix, load, write in forms:
+            got = ctypes.c_size_t()
+            assert write(params.h, None, 0, ctypes.byref(got)) == 0
+            buf = np.zeros(got.value, dtype=np.uint8)
+
+            def do_write():
+                code = write(params.h, ptr(buf), buf.size, ctypes.byref(got))
+                assert code == 0 and got.value == buf.size, (code, got.value)
+
+            loaded = []
+
+            def do_load():
+                h = ctypes.c_void_p()
+                code = load(ctx.h, ptr(buf), buf.size, 0, ctypes.byref(h))
+                assert code == 0, code
+                loaded.append(h)
+
+            t_write, t_load = [], []
+            for _ in range(args.reps + 1):  # one warm-up of each
+                t_write.append(timed(do_write)[1])
+                t_load.append(timed(do_load)[1])
+                while len(loaded) > 1:
+                    lib.bh_params_free(loaded.pop(0))
+            rec["write" + suffix] = summary(t_write[1:], int(buf.size))
+            rec["load" + suffix] = summary(t_load[1:], int(buf.size))
+            # what was loaded writes the file it came from
+            back = np.zeros(buf.size, dtype=np.uint8)
+            assert write(loaded[0], ptr(back), back.size, ctypes.byref(got)) == 0 and bytes(back) == bytes(buf)
+            lib.bh_params_free(loaded.pop())
+        print(json.dumps(rec), flush=True)
+        del params
     ctx.close()
 
 
