@@ -332,12 +332,29 @@ BH_DEV Fe<C> fe_reduce_full(Fe<C> x) {
   return x;
 }
 
-// x ≡ 0 (mod p), valid for x < 128p.  x = k*p exactly when the low limb gives
-// k = x0 * p^-1 mod 2^29 < 128 and the full comparison with k*p succeeds.
+// The largest k < 128 whose multiple k*p fits the N limbs: min(127, (2^(BITS*N) - 1) / p).
+// 127 for DFp (128p < 2^388 in 406 bits), 70 for Fr (71r > 2^261).  The inner loop is the limb
+// product k*p; no carry out of the top limb means k*p < 2^(BITS*N).  Compile time only.
+template <class C>
+constexpr uint32_t fe_is_zero_kmax() {
+  for (uint32_t k = 127; k > 0; k--) {
+    uint64_t carry = 0;
+    for (int i = 0; i < C::N; i++) carry = ((uint64_t)C::P[i] * k + carry) >> C::BITS;
+    if (carry == 0) return k;
+  }
+  return 0;
+}
+
+// x ≡ 0 (mod p).  Preconditions: x < 128p, and x in normalised limbs (every limb <= MASK, so
+// x < 2^(BITS*N)).  x = k*p exactly when the low limb gives k = x0 * p^-1 mod 2^29, k*p fits the
+// limbs (k <= fe_is_zero_kmax) and the full comparison with k*p succeeds.  The comparison drops the
+// carry out of the top limb, so without the bound on k it would also accept k*p - 2^(BITS*N): for
+// Fr, 71r - 2^261 .. 127r - 2^261, every one of them the Montgomery form of -1.
 template <class C>
 BH_DEV bool fe_is_zero(const Fe<C>& x) {
+  constexpr uint32_t KMAX = fe_is_zero_kmax<C>();
   const uint32_t k = (x.v[0] * C::P0INV) & C::MASK;
-  if (k >= 128u) return false;
+  if (k > KMAX) return false;
   uint64_t carry = 0;
   uint32_t diff = 0;
 #pragma unroll
@@ -348,6 +365,7 @@ BH_DEV bool fe_is_zero(const Fe<C>& x) {
   }
   return diff == 0;
 }
+static_assert(fe_is_zero_kmax<FpCfg>() == 127 && fe_is_zero_kmax<FrCfg>() == 70, "fe_is_zero: multiples that fit");
 
 template <class C>
 BH_DEV bool fe_is_zero_canonical(const Fe<C>& x) {

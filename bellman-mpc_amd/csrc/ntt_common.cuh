@@ -26,6 +26,12 @@ __device__ __forceinline__ DFr ld_limbs(const uint32_t* t, size_t i) {  // unpac
   for (int k = 0; k < 9; k++) r.v[k] = t[i * 9 + k];
   return r;
 }
+// x == 0 mod r for x < 2r in normalised limbs: exact, by reducing below r and comparing every limb
+// with zero.  The one zero test on Fr scalars of k_r1cs_ext, k_r1cs_unsatisfied and k_pcheck_flags
+// (fe_is_zero's x == k r would do for x < 2r too, but needs the range argument of field.cuh)
+__device__ __forceinline__ bool fr_is_zero_below_2r(const DFr& x) {
+  return fe_is_zero_canonical<FrCfg>(fe_csub<FrCfg, 1>(x));
+}
 __device__ __forceinline__ uint32_t brev(uint32_t x, int bits) {
   return bits ? (__builtin_bitreverse32(x) >> (32 - bits)) : 0u;
 }

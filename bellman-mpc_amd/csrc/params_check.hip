@@ -26,22 +26,18 @@ using namespace bh;
 
 namespace bh {
 
-// x < 2r: x == 0 mod r.  (Not fe_is_zero: for Fr its test also accepts the Montgomery form of -1,
-// see k_r1cs_unsatisfied.)
-__device__ __forceinline__ bool pc_is_zero(const DFr& x) {
-  return fe_is_zero_canonical<FrCfg>(fe_csub<FrCfg, 1>(x));
-}
 // device Montgomery (< 2r) -> the canonical value (x * 2^-261 <= r, as k_scalars_prepare)
 __device__ __forceinline__ DFr pc_canonical(const DFr& x) {
   return fe_csub<FrCfg, 1>(fe_from_mont<FrCfg>(x));
 }
 
-// y: u | v | w, n each (packed device Montgomery, < 2r)
+// y: u | v | w, n each (packed device Montgomery, < 2r).  The same exact test as the generator's
+// k_r1cs_ext (ntt_common.cuh: fr_is_zero_below_2r), so both call the same columns present
 __global__ void __launch_bounds__(256) k_pcheck_flags(const uint32_t* y, uint32_t n, uint32_t* fu, uint32_t* fv) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  fu[j] = pc_is_zero(ld_packed(y, j)) ? 0u : 1u;
-  fv[j] = pc_is_zero(ld_packed(y, (size_t)n + j)) ? 0u : 1u;
+  fu[j] = fr_is_zero_below_2r(ld_packed(y, j)) ? 0u : 1u;
+  fv[j] = fr_is_zero_below_2r(ld_packed(y, (size_t)n + j)) ? 0u : 1u;
 }
 
 // pos: the exclusive scan of flag, so pos[j] < the number of set flags <= n

@@ -122,9 +122,13 @@ __global__ void __launch_bounds__(256) k_r1cs_ext(const uint32_t* y, uint32_t n,
   const DFr t = fe_add<FrCfg>(fe_add<FrCfg>(fe_mul<FrCfg>(u, ld_const(c.beta)), fe_mul<FrCfg>(v, ld_const(c.alpha))), w);
   const DFr e = fe_mul<FrCfg>(t, ld_const(j < ni ? c.gamma_inv : c.delta_inv));
   st_canonical(ext, j, e);
-  fu[j] = fe_is_zero<FrCfg>(u) ? 0u : 1u;
-  fv[j] = fe_is_zero<FrCfg>(v) ? 0u : 1u;
-  if (j >= ni && fe_is_zero<FrCfg>(e)) atomicAdd(unconstrained, 1u);
+  // u, v < 2r as they were stored (fr_acc).  e < 2r by fe_mul's contract (field.cuh): a < A r and
+  // b < B r give (a b + m r) / 2^261 with m < 2^261, which is < (A B r / 2^261 + 1) r < 2r when
+  // A B r < 2^261; here A = 6, B = 1 and 2^261 / r > 70.  The test is exact: -1, held as
+  // r - (2^261 mod r) or that plus r, is not zero (generator.rs:500-510, 582-590, 614-632)
+  fu[j] = fr_is_zero_below_2r(u) ? 0u : 1u;
+  fv[j] = fr_is_zero_below_2r(v) ? 0u : 1u;
+  if (j >= ni && fr_is_zero_below_2r(e)) atomicAdd(unconstrained, 1u);
 }
 
 __global__ void __launch_bounds__(256) k_r1cs_compact(const uint32_t* y, const uint32_t* flag, const uint32_t* pos,
@@ -214,17 +218,18 @@ __global__ void __launch_bounds__(256) k_r1cs_row_segments(const uint32_t* coeff
   st_packed(part, k, acc);
 }
 
-// abc: a | b | c, m each, < 2r.  a b < 2r and c < 2r: the difference (+ 2r) is < 4r and is reduced
-// to [0, r) before it is compared with zero.  (fe_is_zero's test x == k r is not used here: nine
-// limbs hold 261 bits and 71 r is more, so for Fr it also accepts 71 r - 2^261 = r - (2^261 mod r),
-// the Montgomery form of -1 -- precisely a constraint whose c is too large by one.)
+// abc: a | b | c, m each, < 2r.  a b < 2r and c < 2r: the difference (+ 2r) is < 4r; it is brought
+// below 2r and tested exactly (ntt_common.cuh: fr_is_zero_below_2r).  A test that took the
+// Montgomery form of -1, r - (2^261 mod r), for zero -- as fe_is_zero did for Fr before it bounded
+// its k by the multiples of r that fit nine limbs -- would pass precisely a constraint whose c is
+// too large by one.
 __global__ void __launch_bounds__(256) k_r1cs_unsatisfied(const uint32_t* abc, uint32_t m, uint32_t nc,
                                                           uint32_t* first) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nc) return;
   const DFr ab = fe_mul<FrCfg>(ld_packed(abc, i), ld_packed(abc, (size_t)m + i));
   const DFr d = fe_sub<FrCfg, 2>(ab, ld_packed(abc, 2 * (size_t)m + i));
-  if (!fe_is_zero_canonical<FrCfg>(fe_csub<FrCfg, 1>(fe_csub<FrCfg, 2>(d)))) atomicMin(first, i);
+  if (!fr_is_zero_below_2r(fe_csub<FrCfg, 2>(d))) atomicMin(first, i);
 }
 
 void r1cs_kernels(std::vector<KernInfo>& v) {

@@ -103,6 +103,14 @@ def _fr_cases():
         cs.append((rng.randrange(8 * R), rng.randrange(2 * R), {"sub2": 1, "add": 1}))
     for v in [0, 1, R - 1, (1 << 256) - 1] + [1 << i for i in range(256)] + [rng.randrange(1 << 256) for _ in range(256)]:
         cs.append((v, 0, {"pack": 1}))
+    # k r for the k whose multiple does not fit the nine limbs, less the 2^261 a comparison that drops
+    # the top carry loses: all 57 are = -2^261 mod r, the device Montgomery form of -1, not zero
+    for k in range(FR_TOP // R + 1, 128):
+        x = k * R - FR_TOP
+        assert 0 < x < FR_TOP and x % R == -FR_TOP % R
+        cs.append((x, 0, {"zero": False, "csub1": 1, "csub2": 1}))
+        for y in (x + 1, x - 1, x + (1 << BITS)):
+            cs.append((y, 0, {"zero": False}))
     return cs
 
 
