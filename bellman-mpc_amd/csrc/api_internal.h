@@ -215,6 +215,14 @@ extern "C" bh_status bh_selftest_accumulate(int device, int group, int kernel, c
                                             const uint32_t* offsets, size_t nbt, uint32_t S, uint32_t b_lo,
                                             uint32_t b_hi, uint32_t* bucket_sums, uint32_t* conts,
                                             uint32_t* cont_bucket);
+// selftest.hip (tests/test_gpu_reduce.py): the accumulation and then the real back half
+// (max_span, msm_back -> reduce_range) on the same kind of entry list, Wb windows of NB buckets
+// reduced over [b0, b0 + nbr); mode 0: with max_span's device words, 1: without span words
+// (msm_selftest_reduce in msm_impl.cuh)
+extern "C" bh_status bh_selftest_reduce(int device, int group, int mode, const uint32_t* bases, size_t nbases,
+                                        uint32_t rec, const uint32_t* entries, size_t n_entries,
+                                        const uint32_t* offsets, size_t nbt, uint32_t S, uint32_t Wb, uint32_t NB,
+                                        uint32_t b0, uint32_t nbr, uint32_t* bucket_sums, uint32_t* out, int* lc);
 // selftest.hip (tests/test_gpu_digit_sort.py): the layer of msm_common.hip between a caller's
 // scalars and the accumulation kernels, through the host functions of msm.h on validated host
 // arrays: sort_entries + max_span, derive_sorted, exclusive_scan and its device-bounded form

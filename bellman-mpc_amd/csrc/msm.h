@@ -129,6 +129,16 @@ hipError_t msm_selftest_accumulate(int kernel, const uint32_t* h_bases, size_t n
                                    const uint32_t* h_entries, size_t E, const uint32_t* h_offsets, size_t nbt,
                                    uint32_t S, uint32_t b_lo, uint32_t b_hi, uint32_t* h_bucket_sums, uint32_t* h_conts,
                                    uint32_t* h_cont_bucket);
+// The back half on a caller-ordered entry list the caller has validated (bh_selftest_reduce,
+// selftest.hip): msm_accumulate, then max_span over the reduced range and msm_back with its words
+// (mode 0) or msm_back without span words (mode 1), on a shape of Wb windows of NB buckets with one
+// digit window (n = E) -- a bucket shard [b0, b0 + nbr) unless the range is every bucket.  Returns
+// bucket_sums[Wb * NB] as k_cont_fold left them (0xFF bytes where nothing was written) and
+// msm_back's output points: Wb totals, 2 for one shared window, 3 for a bucket shard.
+template <class C>
+hipError_t msm_selftest_reduce(int mode, const uint32_t* h_bases, size_t nbases, uint32_t rec,
+                               const uint32_t* h_entries, size_t E, const uint32_t* h_offsets, uint32_t S, uint32_t Wb,
+                               uint32_t NB, uint32_t b0, uint32_t nbr, uint32_t* h_bucket_sums, uint32_t* h_out);
 template <class C>
 hipError_t msm_front(MsmWorkspace<C>& ws, hipStream_t st, const uint32_t* d_bases, const uint32_t* d_scalars,
                      size_t n, const int32_t* d_idx, uint32_t base_offset, const MsmShape& sh, MsmTiming* timing);

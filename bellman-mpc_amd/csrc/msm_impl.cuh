@@ -2,6 +2,8 @@
 // msm_g1.hip / msm_g2.hip so the two instantiations compile in parallel).
 #pragma once
 #include <cstdlib>
+#include <cstring>
+#include <vector>
 
 #include "msm.h"
 #include <algorithm>
@@ -998,6 +1000,63 @@ hipError_t msm_selftest_accumulate(int kernel, const uint32_t* h_bases, size_t n
   if ((e = hipMemcpy(h_bucket_sums, sums.p, nbt * sizeof(Pt), hipMemcpyDeviceToHost)) != hipSuccess) return e;
   if ((e = hipMemcpy(h_conts, conts.p, segs * sizeof(Pt), hipMemcpyDeviceToHost)) != hipSuccess) return e;
   return hipMemcpy(h_cont_bucket, cb.p, segs * 4, hipMemcpyDeviceToHost);
+}
+
+// The back half on an entry list in the caller's order (msm.h; the arguments are validated by
+// bh_selftest_reduce).  The list stands in a workspace as a sort would have left it -- entries,
+// offsets, counts = the offsets' differences -- under a shape of one digit window (W = 1, n = E)
+// with the caller's Wb, NB and S, a bucket shard [b0, b0 + nbr) when the range is not the whole of
+// the buckets; bucket_sums, conts and cont_bucket start as 0xFF bytes.  Then what a multiexp runs:
+// msm_accumulate, max_span over the reduced range (mode 0) and msm_back with max_span = -1.
+template <class C>
+hipError_t msm_selftest_reduce(int mode, const uint32_t* h_bases, size_t nbases, uint32_t rec,
+                               const uint32_t* h_entries, size_t E, const uint32_t* h_offsets, uint32_t S, uint32_t Wb,
+                               uint32_t NB, uint32_t b0, uint32_t nbr, uint32_t* h_bucket_sums, uint32_t* h_out) {
+  using Pt = typename C::P;
+  const size_t nbt = (size_t)Wb * NB, segs = (E + S - 1) / S;
+  MsmShape sh{};
+  sh.W = 1;
+  sh.NB = (int)NB;
+  sh.S = (int)S;
+  sh.Wb = (int)Wb;
+  sh.rec = (int)rec;
+  if (b0 != 0 || nbr != NB) {
+    sh.bk_lo = b0;
+    sh.bk_hi = b0 + nbr;
+  }
+  struct Ws : MsmWorkspace<C> {
+    void *bases = nullptr, *span = nullptr;
+    ~Ws() {
+      if (bases) (void)hipFree(bases);
+      if (span) (void)hipFree(span);
+      this->release();
+    }
+  } ws;
+  std::vector<uint32_t> counts(nbt + 1, 0u);
+  for (size_t b = 0; b < nbt; b++) counts[b] = h_offsets[b + 1] - h_offsets[b];
+  hipError_t e;
+  if ((e = ws.grow(E, nbt, segs + 1, reduce_partial_points(sh, sizeof(Pt) > 256))) != hipSuccess) return e;
+  if ((e = hipMalloc(&ws.bases, nbases * rec * 4)) != hipSuccess) return e;
+  if ((e = hipMalloc(&ws.span, MAX_SPAN_BLOCKS * 4)) != hipSuccess) return e;
+  if ((e = hipMemcpy(ws.bases, h_bases, nbases * rec * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
+  if ((e = hipMemcpy(ws.entries, h_entries, E * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
+  if ((e = hipMemcpy(ws.offsets, h_offsets, (nbt + 1) * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
+  if ((e = hipMemcpy(ws.counts, counts.data(), (nbt + 1) * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
+  if ((e = hipMemset(ws.bucket_sums, 0xff, nbt * sizeof(Pt))) != hipSuccess) return e;
+  if ((e = hipMemset(ws.conts, 0xff, (segs + 1) * sizeof(Pt))) != hipSuccess) return e;
+  if ((e = hipMemset(ws.cont_bucket, 0xff, (segs + 1) * 4)) != hipSuccess) return e;
+  if ((e = hipMemset(ws.span, 0xff, MAX_SPAN_BLOCKS * 4)) != hipSuccess) return e;
+  if ((e = msm_accumulate<C>(ws, nullptr, (const uint32_t*)ws.bases, E, sh, nullptr)) != hipSuccess) return e;
+  if (mode == 0 && (e = max_span(ws.counts + sh.red_lo(), ws.offsets + sh.red_lo(), (size_t)Wb * sh.red_nb(), S,
+                                 (uint32_t*)ws.span, nullptr, nullptr)) != hipSuccess)
+    return e;
+  if ((e = msm_back<C>(ws, nullptr, E, sh, ws.host_window_sums, -1, nullptr,
+                       mode == 0 ? (const uint32_t*)ws.span : nullptr)) != hipSuccess)
+    return e;
+  if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
+  const size_t outs = sh.bucket_shard() ? 3 : (Wb == 1 ? 2 : Wb);
+  memcpy(h_out, ws.host_window_sums, outs * sizeof(Pt));
+  return hipMemcpy(h_bucket_sums, ws.bucket_sums, nbt * sizeof(Pt), hipMemcpyDeviceToHost);
 }
 
 // Front half of one multiexp: sort + accumulation, stream-ordered on st.

@@ -199,6 +199,53 @@ extern "C" bh_status bh_selftest_accumulate(int device, int group, int kernel, c
   return BH_OK;
 }
 
+// The back half of a multiexp (msm_impl.cuh: msm_accumulate, max_span, msm_back -> reduce_range)
+// on an entry list in the caller's order: Wb windows of NB buckets (nbt = Wb * NB), reduced over
+// [b0, b0 + nbr) of one shared window (Wb == 1) or over every window (b0 = 0, nbr = NB).  mode 0:
+// max_span's words over the reduced range are handed to the kernels, as the prover and the job
+// queue run a tail; mode 1: no span words, every level of the continuation tree, as
+// msm_window_sums runs it.  Checked here, nothing launched on a violation: the rules of
+// bh_selftest_accumulate for sizes, rec, offsets, base indices and S; Wb <= 128, Wb * NB == nbt;
+// nbr a power of two, or with Wb == 1 a multiple of 1024; b0 + nbr <= NB, and for Wb > 1 the
+// whole windows; at least one entry in the range.
+// Returns bucket_sums[nbt] as k_cont_fold left them (raw XYZZ limbs; buckets outside the range or
+// without entries: 0xFF bytes), k_rowcol_final's points in out -- Wb totals for Wb > 1, out[0..1]
+// for the whole of one shared window, out[0..2] for a proper range of it (the bucket-shard path) --
+// and the geometry's lc: a shared window's total is out[0] + 2^lc * out[1].
+extern "C" bh_status bh_selftest_reduce(int device, int group, int mode, const uint32_t* bases, size_t nbases,
+                                        uint32_t rec, const uint32_t* entries, size_t n_entries,
+                                        const uint32_t* offsets, size_t nbt, uint32_t S, uint32_t Wb, uint32_t NB,
+                                        uint32_t b0, uint32_t nbr, uint32_t* bucket_sums, uint32_t* out, int* lc) {
+  constexpr size_t CAP = (size_t)1 << 16;
+  if (!bases || !entries || !offsets || !bucket_sums || !out || !lc) return BH_ERR_INVALID_ARGUMENT;
+  if ((group != 0 && group != 1) || (mode != 0 && mode != 1)) return BH_ERR_INVALID_ARGUMENT;
+  const uint32_t packed = group ? 2u * Fp2Ops::PACKED_WORDS : 2u * G1F::PACKED_WORDS;
+  const uint32_t table = group ? bh::G2_TABLE_REC : bh::G1_TABLE_REC;
+  if (rec != packed && rec != table) return BH_ERR_INVALID_ARGUMENT;
+  if (!nbases || nbases > CAP || !n_entries || n_entries > CAP || !nbt || nbt > CAP) return BH_ERR_INVALID_ARGUMENT;
+  if (S < 1 || S > CAP) return BH_ERR_INVALID_ARGUMENT;
+  if (Wb < 1 || Wb > 128 || NB < 1 || NB > CAP || (size_t)Wb * NB != nbt) return BH_ERR_INVALID_ARGUMENT;
+  if (nbr < 1 || nbr > NB || b0 > NB - nbr) return BH_ERR_INVALID_ARGUMENT;
+  const bool pow2 = (nbr & (nbr - 1)) == 0;
+  if (Wb > 1 ? !(pow2 && b0 == 0 && nbr == NB) : !(pow2 || nbr % bh::BUCKET_SHARD_GRANULE == 0))
+    return BH_ERR_INVALID_ARGUMENT;
+  if (offsets[0] != 0 || offsets[nbt] != n_entries) return BH_ERR_INVALID_ARGUMENT;
+  for (size_t b = 0; b < nbt; b++)
+    if (offsets[b] > offsets[b + 1]) return BH_ERR_INVALID_ARGUMENT;
+  if (offsets[b0] == offsets[b0 + (size_t)Wb * nbr]) return BH_ERR_INVALID_ARGUMENT;
+  for (size_t j = 0; j < n_entries; j++)
+    if ((entries[j] & 0x7fffffffu) >= nbases) return BH_ERR_INVALID_ARGUMENT;
+  BH_TRY_HIP(hipSetDevice(device));
+  if (group)
+    BH_TRY_HIP(bh::msm_selftest_reduce<G2Ops>(mode, bases, nbases, rec, entries, n_entries, offsets, S, Wb, NB, b0, nbr,
+                                              bucket_sums, out));
+  else
+    BH_TRY_HIP(bh::msm_selftest_reduce<G1Ops>(mode, bases, nbases, rec, entries, n_entries, offsets, S, Wb, NB, b0, nbr,
+                                              bucket_sums, out));
+  *lc = bh::rowcol_geom(nbr, bh::ROWCOL_QLG, group != 0).lc;
+  return BH_OK;
+}
+
 // n cases of 8 Fp operands a .. h (14 raw limbs each; e .. h < 2^386, fe2_mul_sub_kara's bound) and
 // 2 Fr operands x, y (9 raw limbs each) -> per case, once per column form (split, then
 // carry-seeded): a*b, a^2, a*b + c*d, a/R (Fp); (a + b u)(c + d u) by fe2_mul_kara (c0, c1);

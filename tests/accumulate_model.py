@@ -10,9 +10,35 @@ Sorted entries lie bucket after bucket (offsets[b] .. offsets[b + 1]); thread s 
   * otherwise cont_bucket[s] = NONE, when the clipped segment starts at s S;
   * nothing else is written.
 Used by test_accumulate_model_cpu.py (over the integers mod r) and test_gpu_accumulate.py (over G1
-and G2 through the oracle)."""
+and G2 through the oracle).  bucket_totals and range_sums say what the back half (reduce_range)
+must make of those pieces: test_gpu_reduce.py, test_reduce_layout_cpu.py."""
 
 NONE = 0xFFFFFFFF
+
+
+def bucket_totals(values, offsets, b_lo, b_hi, add, zero):
+    """What the continuation folds (k_cont_seq, k_cont_long, k_cont_treeF, k_cont_fold) must leave
+    in bucket_sums[b]: the plain sum of the bucket's entries, for every non-empty bucket of
+    [b_lo, b_hi)."""
+    out = {}
+    for b in range(b_lo, b_hi):
+        if offsets[b + 1] > offsets[b]:
+            acc = zero
+            for j in range(offsets[b], offsets[b + 1]):
+                acc = add(acc, values[j])
+            out[b] = acc
+    return out
+
+
+def range_sums(totals, b0, nbr, add, zero):
+    """(sum_b (b - b0 + 1) B_b, sum_b B_b) over the buckets [b0, b0 + nbr) -- bucket b0 + i holds
+    digit i + 1 of the range -- by the serial running sum of multiexp.rs."""
+    run, acc = zero, zero
+    for b in range(b0 + nbr - 1, b0 - 1, -1):
+        if b in totals:
+            run = add(run, totals[b])
+        acc = add(acc, run)
+    return acc, run
 
 
 def expected(values, offsets, S, b_lo, b_hi, add, zero):

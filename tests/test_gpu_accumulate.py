@@ -49,16 +49,21 @@ def _fn():
     return f
 
 
-@functools.lru_cache(maxsize=None)
-def _bases(name):
-    """affine base points; the scalars are chosen, the sums follow"""
-    c = GROUPS[name].curve
+def _scalars():
+    """the bases' scalars: chosen, with C = A + B, F = D + E, NC = -C"""
     rng = random.Random(5)
     ks = [rng.randrange(1, 1 << 64) for _ in range(NBASES)]
     ks[C] = ks[A] + ks[B]
     ks[F] = ks[D] + ks[E]
     ks[NC] = bls.R - ks[C]
-    return tuple(c.to_affine(c.mul(c.generator(), k)) for k in ks)
+    return tuple(ks)
+
+
+@functools.lru_cache(maxsize=None)
+def _bases(name):
+    """affine base points; the scalars are chosen, the sums follow"""
+    c = GROUPS[name].curve
+    return tuple(c.to_affine(c.mul(c.generator(), k)) for k in _scalars())
 
 
 def _records(grp, rec):

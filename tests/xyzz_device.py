@@ -1,6 +1,6 @@
 """Raw device limbs <-> Python integers, and the checks every device XYZZ point must pass.
 
-Shared by test_gpu_group_law.py and test_gpu_accumulate.py.  A device Fp value is 14 little-endian
+Shared by test_gpu_group_law.py, test_gpu_accumulate.py and test_gpu_reduce.py.  A device Fp value is 14 little-endian
 29-bit limbs in Montgomery form (x * 2^406 mod p), any representative the bounds of
 csrc/curve.cuh allow; an Fp2 value is two of them (c0, c1).  Field elements are tuples of
 integer components here (1 for G1, 2 for G2); the expected points come from oracle/bls12_381.py.
